@@ -1,7 +1,15 @@
 """Benchmark: batched PBN env-steps/s (BASELINE.json metric) on 1..8 MI355X.
 
     python bench.py [--gpus N --steps K --warmup W]          # N > 1: spawns N ranks itself
+    python bench.py --full [...]                             # + every other line this benchmark measures
+    python bench.py --dump-outputs DIR [...]                 # + the last timed step's outputs as DIR/*.npy
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps once and prints one JSON line (``value``,
+``ms_per_step``, the roofline priced on that time).  ``--full`` adds, each in runs of its own
+after the headline's: the same steps between torch's default events, three repeats and the
+event floor, the settle-law line, the hand-off passes (``value_with_gather``), the BDQ
+frame's longest launch and the fused update alone, the CPU baselines and config 1.
 
 A "step" is one synchronous PBN transition of every env of the batch:
 in-kernel random interventions (3 uniform actions per env, the explore policy
@@ -14,9 +22,9 @@ step instead.  The launches of the timed run are captured in one hipGraph.
 Default workload = BASELINE config 2: Bittner-28 (kaban/pbn28.ispl + the 14
 fixture attractors), 65,536 envs per GPU, horizon 20, p = 0.01.
 
-One process per GPU, RCCL ("nccl") process group over all ranks (world 1 too).
+One process per GPU, RCCL ("nccl") process group over all ranks (at world 1 under --full only).
 Multi-GPU is weak scaling: every rank owns its own env range (env_offset =
-rank * envs).  ``value`` times the steps alone; ``value_with_gather`` times the
+rank * envs).  ``value`` times the steps alone; ``value_with_gather`` (--full) times the
 same steps with the rollout's (s, a, s', r, flags) records (17 B per env-step for
 Bittner-28) handed to the learner (rank 0) after every rollout launch, overlapped
 with the next launch (``gather.all_gather`` times the
@@ -26,6 +34,10 @@ system-scope fence: the interval is the device's work; timing.default_events tim
 the same run between torch's default events), and the max over ranks is reported.  Inputs are resident in HBM before timing.  Before the timed region
 the captured run is replayed untimed for at least --clock-warm seconds so the
 GPU clocks have ramped (the W warmup steps alone are microseconds of GPU work).
+Every timed run then starts from the envs as the first 2,000 steps' worth of those replays left
+them (state, targets, episode steps and the RNG's step index are rewound), so what it computes
+does not depend on how many replays the ramp took; ``--dump-outputs`` writes the last timed
+step's outputs.
 """
 from __future__ import annotations
 
@@ -101,6 +113,19 @@ def parse():
     p.add_argument("--clock-warm", type=float, default=0.3,
                    help="seconds of untimed replays of the captured run before timing (GPU clock ramp)")
     p.add_argument("--cpu-seconds", type=float, default=10.0)
+    p.add_argument("--full", action="store_true",
+                   help="after the headline run, also everything else this benchmark measures, each in runs of "
+                        "its own: the same steps between torch's default events, three repeats, the event floor, "
+                        "the settle-law line, the hand-off passes (value_with_gather), the longest launch and the "
+                        "fused update alone (bdq workloads), the CPU baselines and config 1.  Without it the run "
+                        "sets up, warms up, times the --steps steps once and prints the result line; the "
+                        "--no-cpu-baseline, --no-gather, --settle-line and --cpu-seconds options act under --full")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what their last step left with the caller (rank 0's envs) as "
+                        "DIR/<name>.npy: float32, or float64 for the packed 32-bit words; at most 64 MB in all (a "
+                        "fixed, seeded sample of the envs above that, its indices in env_index.npy).  The timed "
+                        "steps start from envs kept after a fixed number of untimed steps, so the same arguments "
+                        "give the same arrays")
     a = p.parse_args()
     bdq = a.workload in ("bdq", "bdq-learn")
     a.learn_graph = False
@@ -438,6 +463,67 @@ def launch_plan(steps: int, chunk: int):
     return [chunk] * full + ([rem] if rem else [])
 
 
+DUMP_BYTES = 64 * 2 ** 20   # --dump-outputs writes at most this much in all
+MIX_STEPS = 2000            # untimed steps after the warmup before the envs every timed run starts from are kept
+
+
+def dump_array(t):
+    """A tensor as --dump-outputs stores it: the packed uint32 words (int32 tensors) and 64-bit
+    values as float64, everything else (f32, the u8 flags, the i16 update counts) as float32;
+    every value is exact in its format."""
+    t = t.detach().cpu()
+    if t.dtype == torch.int32:
+        return (t.to(torch.int64) & 0xFFFFFFFF).to(torch.float64).numpy()
+    if t.dtype in (torch.int64, torch.float64):
+        return t.to(torch.float64).numpy()
+    return t.to(torch.float32).numpy()
+
+
+def last_step_outputs(env, agent=None, rollout_out=None, loss=None) -> dict:
+    """What the last step of the timed path left with its caller, for env.num_envs envs (env = last
+    axis): the env's state, target ids and episode steps, and the step's flip masks, reward and flags
+    (with the observation, s' and update counts where the path stores them).  ``rollout_out``: the
+    last rollout launch's buffers (their last step is taken); else the step launch's own outputs."""
+    k = env.num_envs
+    out = {"state": env.state[:, :k], "target": env.target[:k], "t": env.t[:k]}
+    if rollout_out is not None:
+        for name in ("obs", "flipmask", "reward", "flags", "final_state", "updates"):
+            if rollout_out.get(name) is not None:
+                out[name] = rollout_out[name][-1][..., :k]
+    else:
+        out.update(flipmask=env.flipmask[:, :k], reward=env.reward[:k], flags=env.flags[:k])
+        if env.final_state is not None:
+            out["final_state"] = env.final_state[:, :k]
+        if agent is not None:
+            out["actions"] = agent.actions[:k].t()
+        if loss is not None:
+            out["loss"] = loss.reshape(-1)
+    return {name: dump_array(t) for name, t in out.items()}
+
+
+def dump_outputs(path: str, arrays: dict, n_envs: int, limit: int = DUMP_BYTES, seed: int = 0) -> dict:
+    """Write name -> array as path/<name>.npy, at most `limit` bytes of array data in all.  Above
+    that, the arrays whose last axis is the env axis keep the same fixed sample of the envs
+    (sorted indices drawn without replacement from numpy's default_rng(seed); written as
+    env_index.npy).  Returns what was written."""
+    import numpy as np
+
+    per_env = {k: a for k, a in arrays.items() if a.ndim >= 1 and a.shape[-1] == n_envs}
+    fixed = sum(a.nbytes for k, a in arrays.items() if k not in per_env)
+    row = sum(a.nbytes // n_envs for a in per_env.values())
+    out = dict(arrays)
+    if per_env and fixed + row * n_envs > limit:
+        m = max(0, (limit - fixed) // (row + 8))
+        idx = np.sort(np.random.default_rng(seed).choice(n_envs, size=m, replace=False))
+        for k, a in per_env.items():
+            out[k] = np.ascontiguousarray(a[..., idx])
+        out["env_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(path, f"{k}.npy"), a)
+    return out
+
+
 def max_over_ranks(x: float, world: int, dev) -> float:
     t = torch.tensor([x], dtype=torch.float64, device=dev)
     if world > 1:
@@ -727,8 +813,11 @@ def main():
             os.environ["MASTER_PORT"] = str(s.getsockname()[1])
     dev = torch.device("cuda", local)
     torch.cuda.set_device(dev)
-    # one process per GPU, RCCL ("nccl" on ROCm) over xGMI; world 1 too (the per-rollout gather)
-    torch.distributed.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
+    # one process per GPU, RCCL ("nccl" on ROCm) over xGMI; at world 1 only the hand-off passes
+    # of --full use it
+    use_pg = world > 1 or args.full
+    if use_pg:
+        torch.distributed.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
 
     from pbn_rl_amd.attractors import load_attractors
     from pbn_rl_amd.network import load_network
@@ -802,6 +891,7 @@ def main():
         if args.learn_graph:
             learner.capture()   # frame() replays the captured frame from here on
         torch.cuda.synchronize(dev)
+        first_state = env.state   # the buffer a captured run's first launch reads
         graph = None
         if use_graph:
             # step_index (the RNG time coordinate) advances on the host, so the graph holds
@@ -819,25 +909,53 @@ def main():
                 for i, k in enumerate(plan):
                     launch(k, i)
 
-        # untimed clock ramp: replays of the captured run (no timing, no results kept)
+        # untimed clock ramp: replays of the captured run (no timing, no results kept).  The envs
+        # as the first MIX_STEPS steps' worth of replays leave them (episodes out of step with each
+        # other, as in a long run) are kept: every timed run starts from them, however many
+        # replays the ramp goes on to take.  (The training frames carry a learner's worth of state
+        # and are not rewound: their last step repeats from run to run only when --clock-warm is
+        # shorter than those first replays.)
+        mix_reps = -(-MIX_STEPS // args.steps)
+        snap = None
         warm_reps, t_end = 0, time.perf_counter() + args.clock_warm
         while True:
             run()
             torch.cuda.synchronize(dev)
             warm_reps += 1
-            if time.perf_counter() >= t_end:
+            if warm_reps == mix_reps and args.workload != "bdq-learn":
+                snap = (env.state.clone(), env.target.clone(), env.t.clone(), env.step_index)
+            if warm_reps >= mix_reps and time.perf_counter() >= t_end:
                 break
-        dev_ms, host_s = timed(run, stream, dev, world, local)
-        # the same run between torch's default events (system-scope fence at each event)
-        fenced_ms, _ = timed(run, stream, dev, world, local, system_fence=True)
-        # three more timings of the same K steps on the same clock, reported beside `value` (not
-        # in it): a one-launch run is a single sample, and these show whether it is typical
-        repeat_ms = [timed(run, stream, dev, world, local)[0] for _ in range(3)]
-        # the floor of this timing method: the same gate + event pair around a one-element kernel
-        tiny = torch.zeros(1, device=dev)
-        floor_ms = min(timed(lambda: tiny.add_(1.0), stream, dev, world, local)[0] for _ in range(5))
-        floor_fenced_ms = min(timed(lambda: tiny.add_(1.0), stream, dev, world, local, system_fence=True)[0]
-                              for _ in range(5))
+
+        def timed_run(**kw):
+            if snap is not None:   # rewind to the kept envs (eager launches: the RNG's step index too)
+                (first_state if use_graph else env.state).copy_(snap[0])
+                env.target.copy_(snap[1])
+                env.t.copy_(snap[2])
+                if not use_graph:
+                    env.step_index = snap[3]
+            return timed(run, stream, dev, world, local, **kw)
+
+        dev_ms, host_s = timed_run()
+        dumped = None
+        if args.dump_outputs and rank == 0:
+            learn_loss = learner.last_loss if args.workload == "bdq-learn" else None
+            dumped = last_step_outputs(env, agent, bufs_t[len(plan) - 1] if settle_law else bufs.get(plan[-1]),
+                                       learn_loss)
+        fenced_ms = repeat_ms = floor_ms = floor_fenced_ms = None
+        if args.full:
+            # the same run between torch's default events (system-scope fence at each event)
+            fenced_ms, _ = timed_run(system_fence=True)
+            # three more timings of the same K steps on the same clock, reported beside `value` (not
+            # in it): a one-launch run is a single sample, and these show whether it is typical
+            repeat_ms = [timed_run()[0] for _ in range(3)]
+            # the floor of this timing method: the same gate + event pair around a one-element kernel
+            tiny = torch.zeros(1, device=dev)
+            floor_ms = min(timed(lambda: tiny.add_(1.0), stream, dev, world, local)[0] for _ in range(5))
+            floor_fenced_ms = min(timed(lambda: tiny.add_(1.0), stream, dev, world, local, system_fence=True)[0]
+                                  for _ in range(5))
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, dumped, env.num_envs)
     elapsed = dev_ms * 1e-3
     total_env_steps = world * args.envs * args.steps
     value = total_env_steps / elapsed
@@ -846,11 +964,11 @@ def main():
     if settle_law:
         settle = settle_stats([bufs_t[i]["updates"] for i in range(len(plan))], elapsed, total_env_steps)
     settle_other, settle_spec = None, None
-    if rollout_mode and not settle_law and args.workload == "env" and args.settle_line >= 2:
+    if args.full and rollout_mode and not settle_law and args.workload == "env" and args.settle_line >= 2:
         settle_other, settle_spec = settle_line(args, dev, stream, world, local, plan, args.settle_line)
 
     with_gather = None
-    if rollout_mode and not args.no_gather:
+    if args.full and rollout_mode and not args.no_gather:
         with_gather = {}
         # the hand-off of launch k overlaps launch k + 1 (at world 1 the own-shard copy rides along
         # launch k + 1); the last one follows its launch on the launch stream.  A one-launch plan
@@ -875,7 +993,7 @@ def main():
                                 "records": "s, a, s' (final_state), r, flags of every env-step"}
 
     tail_ms = None
-    if args.workload in ("bdq", "bdq-learn") and agent.fused_tail:
+    if args.full and args.workload in ("bdq", "bdq-learn") and agent.fused_tail:
         # the frame's long launch timed alone: 50 back to back, replayed from one hipGraph (eager,
         # the host's ctypes calls would set the pace)
         with torch.cuda.stream(stream):
@@ -888,7 +1006,7 @@ def main():
             tail_ms, _ = timed(tg.replay, stream, dev, world, local)
             tail_ms /= 50
     learn_ms = None
-    if args.workload == "bdq-learn" and learner.fused is not None:
+    if args.full and args.workload == "bdq-learn" and learner.fused is not None:
         # the fused update (pbn_bdq_learn's three launches) timed alone: 50 back to back on the
         # frame's batch rows, replayed from one hipGraph (after the timed frames), with the
         # learner's parameters, Adam state, tables and loss snapshotted before and restored after,
@@ -954,6 +1072,12 @@ def main():
                             "note": "update_policy's FLOPs in the reference's arithmetic (5B row-forwards: online "
                                     "over states and next states, target over next states, backward over B rows, "
                                     "bench.py update_flops) over the fused update's time, 50 replayed back to back"}
+            elif agent.fused_tail:
+                roofline = {"bound": "mfma", "achieved": None, "peak": FP32_MATRIX_TFLOPS, "unit": "TFLOP/s",
+                            "frac": None, "traffic": None,
+                            "kernel": "pbn_qnet_flipmask_from_state (the frame's longest launch)",
+                            "launch_ms": None, "model_flops_utilisation": mfu,
+                            "note": "the longest launch is timed alone under --full"}
             else:
                 roofline = {"bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None,
                             "traffic": None, "kernel": "frame (PyTorch tail)", "launch_ms": frame_ms,
@@ -1021,21 +1145,26 @@ def main():
             "roofline": roofline,
             "timing": {"clock": "HIP events (hipEventDisableSystemFence) on the launch stream behind a spin gate, "
                                 "max over ranks",
-                       "event_floor_us": floor_ms * 1e3,
-                       "default_events": {"value": total_env_steps / (fenced_ms * 1e-3),
-                                          "ms_per_step": fenced_ms / args.steps,
-                                          "event_floor_us": floor_fenced_ms * 1e3,
-                                          "note": "the same run between torch.cuda.Event pairs, whose records "
-                                                  "release device memory to system scope (host visibility)"},
-                       "note": "event_floor_us: the same gate + event pair around a one-element kernel (dispatch "
-                               "and event overhead, part of every timed region)",
-                       "host_ms_per_step": host_s * 1e3 / args.steps, "clock_warm_runs": warm_reps,
-                       "repeats_ms_per_step": [r / args.steps for r in repeat_ms]},
+                       "host_ms_per_step": host_s * 1e3 / args.steps, "clock_warm_runs": warm_reps},
         }
+        if args.full:
+            out["timing"].update({
+                "event_floor_us": floor_ms * 1e3,
+                "default_events": {"value": total_env_steps / (fenced_ms * 1e-3),
+                                   "ms_per_step": fenced_ms / args.steps,
+                                   "event_floor_us": floor_fenced_ms * 1e3,
+                                   "note": "the same run between torch.cuda.Event pairs, whose records "
+                                           "release device memory to system scope (host visibility)"},
+                "note": "event_floor_us: the same gate + event pair around a one-element kernel (dispatch "
+                        "and event overhead, part of every timed region)",
+                "repeats_ms_per_step": [r / args.steps for r in repeat_ms]})
+        if args.dump_outputs:
+            out["dumped_outputs"] = args.dump_outputs
         if rollout_mode:
             kt = kernel_trace(args, plan)
             out["timing"]["launch_us"] = dev_ms * 1e3 / len(plan)
-            out["timing"]["default_events"]["launch_us"] = fenced_ms * 1e3 / len(plan)
+            if args.full:
+                out["timing"]["default_events"]["launch_us"] = fenced_ms * 1e3 / len(plan)
             if kt is not None:
                 kt["value"] = total_env_steps / (kt["avg_launch_us"] * 1e-6 * len(plan))
                 out["timing"]["kernel_trace"] = kt
@@ -1060,7 +1189,7 @@ def main():
         if with_gather is not None:
             out["value_with_gather"] = with_gather["learner"]["value"]
             out["gather"] = with_gather
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             host = host_info()
             threads = host["usable"]
             if args.workload == "bdq-learn":
@@ -1078,7 +1207,8 @@ def main():
             out["host"] = host
         print(json.dumps(out), flush=True)
     env.close()
-    torch.distributed.destroy_process_group()
+    if use_pg:
+        torch.distributed.destroy_process_group()
 
 
 if __name__ == "__main__":

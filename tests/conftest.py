@@ -7,7 +7,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-REFERENCE = "/root/reference"
+GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
 def pytest_configure(config):
@@ -15,7 +15,7 @@ def pytest_configure(config):
 
 
 @pytest.fixture(scope="session")
-def reference_dir():
-    if not os.path.isdir(REFERENCE):
-        pytest.skip("reference checkout not present (GPU box)")
-    return REFERENCE
+def reference_files():
+    """The reference's own data files the suite reads, stored verbatim under tests/golden/:
+    kaban/<name>.ispl (the four network definitions) and pbn7_bdq_final.pt (models/pbn7/bdq_final.pt)."""
+    return GOLDEN

@@ -18,15 +18,17 @@ import numpy as np
 import torch
 
 from pbn_rl_amd.agent import BranchingQNetwork
+from tests.golden_parts import load_parts
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def load_agent(model: str, n: int) -> BranchingQNetwork:
-    """tests/golden/<model>_bdq_final.npz: the reference's trained agent (tools/export_agent.py)."""
-    w = np.load(os.path.join(GOLD, f"{model}_bdq_final.npz"))
+    """tests/golden/<model>_bdq_final.npz (and its .partN.npz): the reference's trained agent
+    (tools/export_agent.py)."""
+    w = load_parts(os.path.join(GOLD, f"{model}_bdq_final.npz"))
     q = BranchingQNetwork((n, n), n + 1, 3)
-    q.load_state_dict({k: torch.from_numpy(w[k]) for k in w.files})
+    q.load_state_dict({k: torch.from_numpy(v) for k, v in w.items()})
     return q.eval()
 
 

@@ -41,8 +41,8 @@ def test_qnet_parameter_count_and_names():
     assert "model.0.bilinear.weight" in names and "adv_heads.2.2.bias" in names
 
 
-def test_reference_checkpoint_loads(reference_dir, golden):
-    path = os.path.join(reference_dir, "models", "pbn7", "bdq_final.pt")
+def test_reference_checkpoint_loads(reference_files, golden):
+    path = os.path.join(reference_files, "pbn7_bdq_final.pt")   # the reference's models/pbn7/bdq_final.pt
     net = load_bdq_checkpoint(BranchingQNetwork((7, 7), 8, 3), path)
     with torch.no_grad():
         q = net(torch.from_numpy(golden["pbn7_x"].astype(np.float32))).numpy()

@@ -56,6 +56,45 @@ def test_parse_defaults(monkeypatch):
     assert a.learn_graph and a.no_graph and not a.no_cpu_baseline   # the training frame's own CPU baseline
 
 
+def test_plain_run_is_the_default(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (20, 5)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_dump_array_formats_are_exact():
+    import numpy as np
+    import torch
+    words = torch.tensor([[-1, 0x7FFFFFFF, -2 ** 31, 5]], dtype=torch.int32)      # uint32 words stored as int32
+    a = bench.dump_array(words)
+    assert a.dtype == np.float64 and a.tolist() == [[2 ** 32 - 1, 2 ** 31 - 1, 2 ** 31, 5]]
+    assert bench.dump_array(torch.tensor([0, 255], dtype=torch.uint8)).dtype == np.float32
+    assert bench.dump_array(torch.tensor([1.5], dtype=torch.float32)).tolist() == [1.5]
+    assert bench.dump_array(torch.tensor([2 ** 40 + 1])).tolist() == [2.0 ** 40 + 1]
+
+
+def test_dump_outputs_keeps_a_fixed_sample_within_the_limit(tmp_path):
+    import numpy as np
+    n = 1000
+    arrays = {"state": np.arange(2 * n, dtype=np.float64).reshape(2, n), "reward": np.arange(n, dtype=np.float32),
+              "loss": np.ones(1, dtype=np.float32)}
+    whole = bench.dump_outputs(str(tmp_path / "whole"), arrays, n)
+    assert sorted(p.name for p in (tmp_path / "whole").iterdir()) == ["loss.npy", "reward.npy", "state.npy"]
+    assert all(np.array_equal(np.load(tmp_path / "whole" / f"{k}.npy"), a) for k, a in whole.items())
+    limit = 4004          # 20 B per env + 8 B per index: 142 envs beside the 4-byte loss
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), arrays, n, limit=limit)
+    got = {p.stem: np.load(p) for p in (tmp_path / "s1").iterdir()}
+    idx = got["env_index"].astype(np.int64)
+    assert len(idx) == 142 and np.all(np.diff(idx) > 0) and sum(a.nbytes for a in got.values()) <= limit
+    assert np.array_equal(got["state"], arrays["state"][:, idx]) and np.array_equal(got["reward"], arrays["reward"][idx])
+    assert np.array_equal(got["loss"], arrays["loss"])
+    assert all(np.array_equal(np.load(tmp_path / "s2" / f"{k}.npy"), a) for k, a in got.items())   # same sample
+
+
 def test_multi_gpu_request_without_gpus_fails_loudly():
     """`bench.py --gpus 2` launches its own ranks; with fewer GPUs than ranks it must refuse
     (exit 2) instead of rehearsing several ranks on one device."""

@@ -77,8 +77,8 @@ def test_compiled_functions_match_python_semantics(name):
 
 
 @pytest.mark.parametrize("name", ["pbn7", "pbn10", "pbn28", "pbn70"])
-def test_bundled_json_matches_reference_ispl(name, reference_dir):
-    net = Network.from_ispl(os.path.join(reference_dir, "kaban", f"{name}.ispl"), name=name)
+def test_bundled_json_matches_reference_ispl(name, reference_files):
+    net = Network.from_ispl(os.path.join(reference_files, "kaban", f"{name}.ispl"), name=name)
     with open(os.path.join(NETWORK_DIR, f"{name}.json")) as f:
         obj = json.load(f)
     assert net.genes == obj["genes"]

@@ -16,6 +16,7 @@ import torch
 
 from pbn_rl_amd.agent import BranchingQNetwork
 from pbn_rl_amd.replay import bdq_update, soft_update
+from tests.golden_parts import load_parts
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "bdq_update.npz")
 GOLD28 = os.path.join(os.path.dirname(__file__), "golden", "bdq_update28.npz")
@@ -59,7 +60,7 @@ def sampled_close(got: torch.Tensor, d, key, n, rtol, atol):
 
 
 def load_fixture():
-    d = np.load(GOLD)
+    d = load_parts(GOLD)   # bdq_update.npz + bdq_update.part2.npz
     return d, [str(n) for n in d["names"]]
 
 

@@ -12,19 +12,20 @@ with them (tests/test_law_pin.py, tests/test_bn_pin.py, tests/test_gpu_law_pin.p
 import os
 import sys
 
-import numpy as np
 import torch
 
 REF = "/root/reference"
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden")
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+from tests.golden_parts import save_parts  # noqa: E402
 
 
 def export(model: str) -> str:
     sd = torch.load(os.path.join(REF, "models", model, "bdq_final.pt"), map_location="cpu", weights_only=True)
     q = {k[2:]: v.detach().to(torch.float32).numpy() for k, v in sd.items() if k.startswith("q.")}
     out = os.path.join(GOLD, f"{model}_bdq_final.npz")
-    np.savez_compressed(out, **q)
-    print("wrote", out, sum(v.size for v in q.values()), "floats")
+    print("wrote", save_parts(out, q), sum(v.size for v in q.values()), "floats")   # parts below 1 MiB
     return out
 
 

@@ -153,8 +153,10 @@ def main():
         keep(f"t2.{n}", n, p.detach().numpy().copy())
     out["losses"] = np.array(losses, dtype=np.float32)
     out["names"] = np.array(names)
-    np.savez_compressed(OUT, **out)
-    print("wrote", OUT, "update_policy lines", lines, "losses", losses, "bytes", os.path.getsize(OUT))
+    from tests.golden_parts import save_parts
+    written = save_parts(OUT, out)   # parts below 1 MiB
+    print("wrote", written, "update_policy lines", lines, "losses", losses, "bytes",
+          [os.path.getsize(p) for p in written])
 
 
 if __name__ == "__main__":

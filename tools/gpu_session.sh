@@ -52,7 +52,7 @@ export TMPDIR=/tmp
 fail() { echo "STEP $1 FAILED"; exit 1; }
 bench() {   # bench NAME ARGS... : one bench line
   local name=$1; shift
-  timeout -k 10 300 python bench.py "$@" > "$out/$name.json" 2> "$out/$name.err" || fail "$name"
+  timeout -k 10 300 python bench.py --full "$@" > "$out/$name.json" 2> "$out/$name.err" || fail "$name"
   echo "$name: $(python -c "import json; d=[json.loads(l) for l in open('$out/$name.json') if l.startswith('{')][-1]; print(d['value'], d.get('roofline',{}).get('frac'))")"
 }
 for step in "$@"; do
@@ -71,19 +71,19 @@ for step in "$@"; do
     bdq)
       bench bench_bdq --workload bdq
       timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/bdq_trace" -o run -- \
-        python bench.py --workload bdq --no-cpu-baseline > "$out/bdq_trace.json" 2> "$out/bdq_trace.err" || fail bdq-trace ;;
+        python bench.py --full --workload bdq --no-cpu-baseline > "$out/bdq_trace.json" 2> "$out/bdq_trace.err" || fail bdq-trace ;;
     bdqpmc)
       timeout -k 10 120 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum --kernel-trace --stats --output-format csv \
-        -d "$out/bdq_pmc_l2" -o run -- python bench.py --workload bdq --no-cpu-baseline > /dev/null 2> "$out/bdq_pmc_l2.err" || fail bdqpmc-l2
+        -d "$out/bdq_pmc_l2" -o run -- python bench.py --full --workload bdq --no-cpu-baseline > /dev/null 2> "$out/bdq_pmc_l2.err" || fail bdqpmc-l2
       timeout -k 10 120 rocprofv3 --pmc FETCH_SIZE --kernel-trace --stats --output-format csv \
-        -d "$out/bdq_pmc_fetch" -o run -- python bench.py --workload bdq --no-cpu-baseline > /dev/null 2> "$out/bdq_pmc_fetch.err" || fail bdqpmc-fetch
+        -d "$out/bdq_pmc_fetch" -o run -- python bench.py --full --workload bdq --no-cpu-baseline > /dev/null 2> "$out/bdq_pmc_fetch.err" || fail bdqpmc-fetch
       timeout -k 10 120 rocprofv3 --pmc WRITE_SIZE --kernel-trace --stats --output-format csv \
-        -d "$out/bdq_pmc_write" -o run -- python bench.py --workload bdq --no-cpu-baseline > /dev/null 2> "$out/bdq_pmc_write.err" || fail bdqpmc-write
+        -d "$out/bdq_pmc_write" -o run -- python bench.py --full --workload bdq --no-cpu-baseline > /dev/null 2> "$out/bdq_pmc_write.err" || fail bdqpmc-write
       echo "bdqpmc done" ;;
     bdq-learn)
       bench bench_bdq_learn --workload bdq-learn
       timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/bdq_learn_trace" -o run -- \
-        python bench.py --workload bdq-learn > "$out/bdq_learn_trace.json" 2> "$out/bdq_learn_trace.err" || fail bdq-learn-trace
+        python bench.py --full --workload bdq-learn > "$out/bdq_learn_trace.json" 2> "$out/bdq_learn_trace.err" || fail bdq-learn-trace
       # (every dispatch's row: tens of MB; the stats stay)
       find "$out/bdq_learn_trace" -name '*kernel_trace.csv' -delete ;;
     stamps)
@@ -109,7 +109,7 @@ for step in "$@"; do
       bench bench_driver --gpus 1 --steps 20 --warmup 5
       bench bench_settle64 --settle 64 --steps 200 --warmup 20 --no-cpu-baseline --no-gather
       timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/settle_trace" -o run -- \
-        python bench.py --settle 64 --steps 200 --warmup 20 --no-cpu-baseline --no-gather \
+        python bench.py --full --settle 64 --steps 200 --warmup 20 --no-cpu-baseline --no-gather \
         > "$out/settle_trace.json" 2> "$out/settle_trace.err" || fail settle-trace ;;
     handoff)
       for plan in 20 10,10; do
@@ -135,11 +135,11 @@ for step in "$@"; do
         nm=${shape%%:*}; args=${shape#*:}
         timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_INSTS_VMEM_WR \
           SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE --kernel-trace --stats --output-format csv \
-          -d "$out/budget_${nm}_a" -o run -- python bench.py --no-cpu-baseline --no-gather --settle-line 0 $args \
+          -d "$out/budget_${nm}_a" -o run -- python bench.py --full --no-cpu-baseline --no-gather --settle-line 0 $args \
           > "$out/budget_${nm}_a.json" 2> "$out/budget_${nm}_a.err" || fail "budget-$nm-a"
         timeout -k 10 300 rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_WAIT_INST_LDS \
           SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_ANY SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE --kernel-trace --stats \
-          --output-format csv -d "$out/budget_${nm}_b" -o run -- python bench.py --no-cpu-baseline --no-gather \
+          --output-format csv -d "$out/budget_${nm}_b" -o run -- python bench.py --full --no-cpu-baseline --no-gather \
           --settle-line 0 $args > "$out/budget_${nm}_b.json" 2> "$out/budget_${nm}_b.err" || fail "budget-$nm-b"
         echo "budget $nm done"
       done ;;
@@ -155,7 +155,7 @@ for step in "$@"; do
         if [ "$lib" = tree ]; then unset PBN_LIB; else export PBN_LIB=$PWD/$lib; fi
         timeout -k 10 300 python -u -m pytest tests/test_gpu_agent.py -m gpu -x -q --timeout 120 --timeout-method thread \
           > "$out/abbdq_${side}_agent.log" 2>&1 || { tail -20 "$out/abbdq_${side}_agent.log"; fail "abbdq $side agent"; }
-        timeout -k 10 300 python bench.py --workload bdq --no-cpu-baseline > "$out/abbdq_$side.json" 2> "$out/abbdq_$side.err" \
+        timeout -k 10 300 python bench.py --full --workload bdq --no-cpu-baseline > "$out/abbdq_$side.json" 2> "$out/abbdq_$side.err" \
           || fail "abbdq $side"
         python -c "import json; d=[json.loads(l) for l in open('$out/abbdq_$side.json') if l.startswith('{')][-1]; r=d['roofline']; print('$side frame_ms', d['ms_per_step'], 'tail_ms', r['launch_ms'], 'bilinear_ms', r.get('bilinear', {}).get('launch_ms'))"
       done
@@ -213,7 +213,7 @@ for step in "$@"; do
         bench absettle_${side}_d20 --gpus 1 --steps 20 --warmup 5 --settle 64 --no-cpu-baseline --no-gather
         bench absettle_${side}_s200 --steps 200 --warmup 20 --settle 64 --no-cpu-baseline --no-gather
         timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --stats --output-format csv \
-          -d "$out/absettle_${side}_write" -o run -- python bench.py --steps 20 --warmup 5 --settle 64 \
+          -d "$out/absettle_${side}_write" -o run -- python bench.py --full --steps 20 --warmup 5 --settle 64 \
           --no-cpu-baseline --no-gather > /dev/null 2> "$out/absettle_${side}_write.err" || fail "absettle $side write"
       done
       unset PBN_LIB ;;
