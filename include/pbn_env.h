@@ -581,6 +581,43 @@ int pbn_host_buffer_free(void* h_ptr);
 /* pbn_stream_sync (ABI 9): waits until the work issued on `stream` has completed. */
 int pbn_stream_sync(void* stream);
 
+/*
+ * Batched control evaluation (model_tester.py:587-658; pbn_rl_amd/evaluate.py): every (source
+ * attractor, target attractor, run) is one env, and a protocol step is act -> pbn_step_dev ->
+ * pbn_eval_track on one stream.  Additive exports (the ABI version is unchanged).
+ *
+ * pbn_eval_track: the bookkeeping of protocol step k = *d_step - step0 + 1 (d_step read when the
+ * kernel runs, as pbn_step_dev reads it; a k outside 1..max_steps touches nothing).  n_alloc is a
+ * multiple of 32, envs i >= n_real are padding.
+ *   d_flags      in     uint8  [n]     the step's flags
+ *   d_actions    in     int32  [n][K]  the acting kernel's actions (nullable without d_strategy)
+ *   d_state      in     uint32 [W][n]  the state after the step
+ *   d_count      in/out int32  [n]
+ *   d_open       in/out uint8  [n]     nonzero = the run has not ended
+ *   d_hit_state  in/out uint32 [W][n]  nullable
+ *   d_strategy   in/out int16  [max_steps][n][K]  nullable
+ *   d_open_after in/out int32  [max_steps + 1]    the caller zeroes it
+ * Per env i < n_real with d_open[i]: strategy[k-1][i][:] = actions[i][:]; if flags[i] has
+ * PBN_FLAG_TERMINATED, count[i] = k, open[i] = 0 and hit_state[:, i] = state[:, i]; else if
+ * k == max_steps, count[i] = max_steps + 1 (the reference's 101, :635) and open[i] = 0.  Closed and
+ * padding envs are neither read for actions nor written.  d_open_after[k] += the envs still open
+ * after the step, one atomic per wave.  1 <= max_steps <= 254 (the step kernels' t is uint8),
+ * K = n_branches 1..64, W = words 1..4; the int32 / uint32 buffers 4-byte, d_strategy 2-byte,
+ * d_step 8-byte aligned.
+ *
+ * pbn_eval_reduce: d_count int32 [n_pairs][runs] (env i = pair * runs + run; runs need not be a
+ * multiple of the wave) -> d_pair_sum int64 [n_pairs] (a failure adds max_steps + 1, the
+ * reference's `+= 101`), d_pair_fail int32 [n_pairs], and d_hist int64 [max_steps + 2] += the
+ * number of runs of every length (bin max_steps + 1 = failures; the caller zeroes it; built per
+ * block in LDS, one atomic per non-empty bin).  Counts outside 0..max_steps + 1 are clamped.
+ */
+int pbn_eval_track(int64_t n_alloc, int64_t n_real, int32_t words, int32_t n_branches, int32_t max_steps,
+                   const int64_t* d_step, int64_t step0, const uint8_t* d_flags, const int32_t* d_actions,
+                   const uint32_t* d_state, int32_t* d_count, uint8_t* d_open, uint32_t* d_hit_state,
+                   int16_t* d_strategy, int32_t* d_open_after, void* stream);
+int pbn_eval_reduce(const int32_t* d_count, int64_t n_pairs, int64_t runs, int32_t max_steps, int64_t* d_pair_sum,
+                    int32_t* d_pair_fail, int64_t* d_hist, void* stream);
+
 const char* pbn_last_error(void);
 int pbn_abi_version(void);
 

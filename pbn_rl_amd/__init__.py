@@ -6,5 +6,6 @@ Public surface:
   spec.EnvSpec                       one environment definition (C descriptor)
   vector_env.VectorPBNEnv            batched envs in HBM, stepped by libpbn_env.so
   env.PBNEnv / make                  scalar gym-style facade (drop-in under train_BDQ.py)
+  evaluate.evaluate_control          source -> target control evaluation of a trained agent
 """
 __version__ = "0.1.0"

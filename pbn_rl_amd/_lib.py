@@ -30,8 +30,8 @@ EXPORTS = ["pbn_net_create", "pbn_net_destroy", "pbn_net_words", "pbn_reset", "p
            "pbn_heads_to_flipmask", "pbn_qnet_heads", "pbn_qnet_flipmask", "pbn_qnet_heads_from_state",
            "pbn_qnet_flipmask_from_state", "pbn_replay_store", "pbn_replay_advance", "pbn_replay_batch", "pbn_bdq_td_loss", "pbn_bdq_layout", "pbn_bdq_learn_workspace",
            "pbn_bdq_pack", "pbn_bdq_image_floats", "pbn_bdq_learn", "pbn_copy_async", "pbn_rollout_copy", "pbn_host_buffer", "pbn_host_buffer_free", "pbn_stream_sync",
-           "pbn_last_error", "pbn_abi_version"]
-SOURCES = ["pbn_env.hip", "pbn_settle.hip", "pbn_agent.hip", "pbn_qnet.hip", "pbn_learn.hip"]
+           "pbn_eval_track", "pbn_eval_reduce", "pbn_last_error", "pbn_abi_version"]
+SOURCES = ["pbn_env.hip", "pbn_settle.hip", "pbn_agent.hip", "pbn_qnet.hip", "pbn_learn.hip", "pbn_eval.hip"]
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -183,6 +183,11 @@ def load() -> ctypes.CDLL:
         L.pbn_host_buffer_free.restype = ctypes.c_int
         L.pbn_stream_sync.argtypes = [vp]
         L.pbn_stream_sync.restype = ctypes.c_int
+    if hasattr(L, "pbn_eval_track"):   # (additive exports of ABI 11: the control evaluation)
+        L.pbn_eval_track.argtypes = [i64, i64, i32, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.pbn_eval_track.restype = ctypes.c_int
+        L.pbn_eval_reduce.argtypes = [vp, i64, i64, i32, vp, vp, vp, vp]
+        L.pbn_eval_reduce.restype = ctypes.c_int
     L.pbn_abi_version.argtypes = []
     L.pbn_abi_version.restype = ctypes.c_int
     _lib = L
