@@ -495,6 +495,19 @@ int pbn_bdq_td_loss(const float* d_online, const float* d_target, const int64_t*
                     float* d_loss, float* d_grad, float* d_scratch, void* stream);
 
 /*
+ * pbn_bdq_td_loss with per-row importance weights (prioritised replay; DDQNPER._learn_step,
+ * ddqn_per/__init__.py:468-483, with the BDQ's MSE).  Additive export (the ABI version is unchanged).
+ *   d_weights  in   float [B]: w_b
+ *   d_priority out  float [B]: |w_b l_b| + replay_constant, l_b = mean_k (expected - current)^2
+ *   d_loss     out  float [1]: mean_b w_b l_b;  d_grad is its gradient (row b's scaled by w_b)
+ * Every other argument as pbn_bdq_td_loss; float buffers 4-byte, d_actions 8-byte aligned.
+ */
+int pbn_bdq_td_loss_per(const float* d_online, const float* d_target, const int64_t* d_actions,
+                        const float* d_rewards, const float* d_masks, const float* d_weights, int32_t batch,
+                        int32_t n_branches, int32_t n_actions, float gamma, float replay_constant, float* d_loss,
+                        float* d_grad, float* d_priority, float* d_scratch, void* stream);
+
+/*
  * The whole update_policy step (bdq_model/__init__.py:100-139) on a flat parameter buffer, for the
  * reference's network BranchingQNetwork((N, N), N + 1, K) (bdq_model/network.py:24-63: bilinear
  * N x N -> 256, trunk 256-128-64-32, K + 1 heads 32-64-(N+1), LeakyReLU).  Replaces the sampled
@@ -617,6 +630,45 @@ int pbn_eval_track(int64_t n_alloc, int64_t n_real, int32_t words, int32_t n_bra
                    int16_t* d_strategy, int32_t* d_open_after, void* stream);
 int pbn_eval_reduce(const int32_t* d_count, int64_t n_pairs, int64_t runs, int32_t max_steps, int64_t* d_pair_sum,
                     int32_t* d_pair_fail, int64_t* d_hist, void* stream);
+
+/*
+ * Proportional prioritised replay (PrioritisedER, bdq_model/memory.py:73-186) over a sum and a min
+ * segment tree held on the device.  Additive exports (the ABI version is unchanged).
+ *
+ * tree_size = T, a power of two >= capacity (the reference takes the smallest); capacity >= 2.
+ * d_sum_tree / d_min_tree are double [2T]: node 1 is the root, leaf i is node T + i, a sum node is
+ * left + right, a min node is min(left, right); the caller initialises every sum node to 0.0 and
+ * every min node to +inf (empty), *d_max_priority to 1.0.  Every entry keeps each ancestor equal to
+ * the operation of its two children, rebuilt level by level.  All counters are read from device
+ * memory when the kernels run, so every launch can be captured in a graph.  Pointers are 8-byte
+ * (float buffers 4-byte) aligned.
+ *
+ * pbn_per_store: the n (1..capacity) transitions stored at ring position *d_pos get the priority
+ *   *d_max_priority ** alpha, at leaves (*d_pos + 1 + j) mod capacity, j < n -- the slot after
+ *   each stored row, as memory.py:114 has it.  *d_pos is the position before the store (the
+ *   caller advances it afterwards).  At most two launches: the touched 512-leaf chunks and their
+ *   subtrees, then the levels above the chunks.
+ * pbn_per_sample: batch (1..1024) rows proportional to priority, one block.  N = *d_size;
+ *   p_total = the sum of leaves [0, N - 2] in the association of the reference's recursion
+ *   (data_structures.py:33-60); row i searches mass = u_i * (p_total / batch) + i * (p_total /
+ *   batch) (find_prefixsum_index) with u_i = ((x << 21) | (y >> 11)) * 2^-53 from the REPLAY Philox
+ *   words (x, y) of (seed, id = i, step = *d_counter); the index is clamped to [0, N - 1].
+ *   d_weights[i] = float((N leaf_i / S) ** -beta / (N min / S) ** -beta), S the sum root, min the
+ *   min root, beta = *d_beta, all in fp64.  Then *d_beta = min(max_beta, beta + beta_step) and
+ *   *d_counter += 1.   d_idx int64 [batch], d_weights float [batch].
+ * pbn_per_update: leaf d_idx[b] = double(d_priorities[b]) ** alpha in both trees, the pairs applied
+ *   in order (of equal indices the highest b wins); *d_max_priority = max of itself and every applied
+ *   priority; pairs with an index outside [0, *d_size) are skipped.  One block, batch 1..1024.
+ */
+int pbn_per_store(int64_t n, const int64_t* d_pos, int64_t capacity, int64_t tree_size, double alpha,
+                  const double* d_max_priority, double* d_sum_tree, double* d_min_tree, void* stream);
+int pbn_per_sample(int32_t batch, int64_t capacity, int64_t tree_size, const int64_t* d_size,
+                   const double* d_sum_tree, const double* d_min_tree, double* d_beta, double max_beta,
+                   double beta_step, uint64_t seed, int64_t* d_counter, int64_t* d_idx, float* d_weights,
+                   void* stream);
+int pbn_per_update(int32_t batch, int64_t capacity, int64_t tree_size, double alpha, const int64_t* d_size,
+                   const int64_t* d_idx, const float* d_priorities, double* d_max_priority, double* d_sum_tree,
+                   double* d_min_tree, void* stream);
 
 const char* pbn_last_error(void);
 int pbn_abi_version(void);

@@ -30,8 +30,10 @@ EXPORTS = ["pbn_net_create", "pbn_net_destroy", "pbn_net_words", "pbn_reset", "p
            "pbn_heads_to_flipmask", "pbn_qnet_heads", "pbn_qnet_flipmask", "pbn_qnet_heads_from_state",
            "pbn_qnet_flipmask_from_state", "pbn_replay_store", "pbn_replay_advance", "pbn_replay_batch", "pbn_bdq_td_loss", "pbn_bdq_layout", "pbn_bdq_learn_workspace",
            "pbn_bdq_pack", "pbn_bdq_image_floats", "pbn_bdq_learn", "pbn_copy_async", "pbn_rollout_copy", "pbn_host_buffer", "pbn_host_buffer_free", "pbn_stream_sync",
-           "pbn_eval_track", "pbn_eval_reduce", "pbn_last_error", "pbn_abi_version"]
-SOURCES = ["pbn_env.hip", "pbn_settle.hip", "pbn_agent.hip", "pbn_qnet.hip", "pbn_learn.hip", "pbn_eval.hip"]
+           "pbn_eval_track", "pbn_eval_reduce", "pbn_per_store", "pbn_per_sample", "pbn_per_update",
+           "pbn_bdq_td_loss_per", "pbn_last_error", "pbn_abi_version"]
+SOURCES = ["pbn_env.hip", "pbn_settle.hip", "pbn_agent.hip", "pbn_qnet.hip", "pbn_learn.hip", "pbn_eval.hip",
+           "pbn_per.hip"]
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -188,6 +190,16 @@ def load() -> ctypes.CDLL:
         L.pbn_eval_track.restype = ctypes.c_int
         L.pbn_eval_reduce.argtypes = [vp, i64, i64, i32, vp, vp, vp, vp]
         L.pbn_eval_reduce.restype = ctypes.c_int
+    if hasattr(L, "pbn_per_store"):   # (additive exports of ABI 11: prioritised replay)
+        f64 = ctypes.c_double
+        L.pbn_per_store.argtypes = [i64, vp, i64, i64, f64, vp, vp, vp, vp]
+        L.pbn_per_store.restype = ctypes.c_int
+        L.pbn_per_sample.argtypes = [i32, i64, i64, vp, vp, vp, vp, f64, f64, u64, vp, vp, vp, vp]
+        L.pbn_per_sample.restype = ctypes.c_int
+        L.pbn_per_update.argtypes = [i32, i64, i64, f64, vp, vp, vp, vp, vp, vp, vp]
+        L.pbn_per_update.restype = ctypes.c_int
+        L.pbn_bdq_td_loss_per.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp]
+        L.pbn_bdq_td_loss_per.restype = ctypes.c_int
     L.pbn_abi_version.argtypes = []
     L.pbn_abi_version.restype = ctypes.c_int
     _lib = L

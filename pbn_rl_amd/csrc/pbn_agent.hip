@@ -465,12 +465,19 @@ __device__ __forceinline__ float td_mean(const float* __restrict__ adv, int A) {
   return s / (float)A;
 }
 
+// kPer (pbn_bdq_td_loss_per; DDQNPER._learn_step, ddqn_per/__init__.py:468-483, with this MSE): row
+// b carries an importance weight w_b.  l_b = mean_k (expected - current)^2, loss = mean_b w_b l_b,
+// g is scaled by w_b, and priority[b] = |w_b l_b| + replay_constant.  Without kPer the kernel is
+// the unweighted one, expression for expression.
+template <bool kPer>
 __global__ void __launch_bounds__(kTdThreads) td_loss_kernel(const float* __restrict__ on, const float* __restrict__ tg,
                                                              const int64_t* __restrict__ actions,
                                                              const float* __restrict__ rewards,
                                                              const float* __restrict__ masks, int B, int K, int A,
                                                              float gamma, float* __restrict__ partial,
-                                                             float* __restrict__ grad) {
+                                                             float* __restrict__ grad,
+                                                             const float* __restrict__ weights,
+                                                             float replay_constant, float* __restrict__ priority) {
   extern __shared__ float sm[];
   const int H = K + 1;
   const int R = kTdRows;
@@ -515,6 +522,7 @@ __global__ void __launch_bounds__(kTdThreads) td_loss_kernel(const float* __rest
     const float d = expected - current;
     sd[t] = d * d;
     sg[t] = 2.f * (current - expected) * inv_bk;
+    if constexpr (kPer) sg[t] *= weights[b];
   }
   __syncthreads();
   // gradient rows of this block, row-major and coalesced: head h, first-half row b0 + r, then the
@@ -535,10 +543,27 @@ __global__ void __launch_bounds__(kTdThreads) td_loss_kernel(const float* __rest
       grad[((size_t)h * rows + B + b0) * A + i] = 0.f;
     }
   }
-  if (t == 0) {
-    float s = 0.f;
-    for (int p = 0; p < nr * K; ++p) s += sd[p];
-    partial[blockIdx.x] = s;
+  if constexpr (kPer) {
+    // row r's weighted loss (and its priority); the rows' terms added in row order
+    if (t < nr) {
+      float l = 0.f;
+      for (int k = 0; k < K; ++k) l += sd[t * K + k];
+      const float wl = weights[b0 + t] * (l / (float)K);
+      priority[b0 + t] = fabsf(wl) + replay_constant;
+      sd[t * K] = wl;             // (this thread alone reads row t of sd)
+    }
+    __syncthreads();
+    if (t == 0) {
+      float s = 0.f;
+      for (int r = 0; r < nr; ++r) s += sd[r * K];
+      partial[blockIdx.x] = s;
+    }
+  } else {
+    if (t == 0) {
+      float s = 0.f;
+      for (int p = 0; p < nr * K; ++p) s += sd[p];
+      partial[blockIdx.x] = s;
+    }
   }
 }
 
@@ -769,13 +794,44 @@ int pbn_bdq_td_loss(const float* d_online, const float* d_target, const int64_t*
   const int H = n_branches + 1;
   const size_t lds = ((size_t)H * 3 * kTdRows * n_actions + 2 * kTdRows * n_branches) * sizeof(float);
   if (lds > 64 * 1024 &&   // (up to 98 KB at 8 heads of 128 actions)
-      hipFuncSetAttribute((const void*)td_loss_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+      hipFuncSetAttribute((const void*)td_loss_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return pbn::set_error(PBN_EDEVICE, "hipFuncSetAttribute failed");
-  hipLaunchKernelGGL(td_loss_kernel, dim3(blocks), dim3(kTdThreads), lds, (hipStream_t)stream, d_online, d_target,
-                     d_actions, d_rewards, d_masks, batch, n_branches, n_actions, gamma, d_scratch, d_grad);
+  hipLaunchKernelGGL(td_loss_kernel<false>, dim3(blocks), dim3(kTdThreads), lds, (hipStream_t)stream, d_online, d_target,
+                     d_actions, d_rewards, d_masks, batch, n_branches, n_actions, gamma, d_scratch, d_grad,
+                     (const float*)nullptr, 0.f, (float*)nullptr);
   if (hipGetLastError() != hipSuccess) return pbn::set_error(PBN_EDEVICE, "td_loss_kernel launch failed");
   hipLaunchKernelGGL(td_loss_sum_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, d_scratch, blocks,
                      1.f / (float)(batch * n_branches), d_loss);
+  if (hipGetLastError() != hipSuccess) return pbn::set_error(PBN_EDEVICE, "td_loss_sum_kernel launch failed");
+  return PBN_OK;
+}
+
+int pbn_bdq_td_loss_per(const float* d_online, const float* d_target, const int64_t* d_actions,
+                        const float* d_rewards, const float* d_masks, const float* d_weights, int32_t batch,
+                        int32_t n_branches, int32_t n_actions, float gamma, float replay_constant, float* d_loss,
+                        float* d_grad, float* d_priority, float* d_scratch, void* stream) {
+  if (batch < 1 || n_branches < 1 || n_branches > 7 || n_actions < 1 || n_actions > 128)
+    return pbn::set_error(PBN_EINVAL, "batch >= 1, n_branches 1..7, n_actions 1..128");
+  if (!d_online || !d_target || !d_actions || !d_rewards || !d_masks || !d_weights || !d_loss || !d_grad ||
+      !d_priority || !d_scratch)
+    return pbn::set_error(PBN_EINVAL, "null buffer");
+  if ((((uintptr_t)d_online | (uintptr_t)d_target | (uintptr_t)d_rewards | (uintptr_t)d_masks | (uintptr_t)d_weights |
+        (uintptr_t)d_loss | (uintptr_t)d_grad | (uintptr_t)d_priority | (uintptr_t)d_scratch) & 3u) != 0 ||
+      ((uintptr_t)d_actions & 7u) != 0)
+    return pbn::set_error(PBN_EINVAL, "float buffers must be 4-byte, d_actions 8-byte aligned");
+  const int blocks = (batch + kTdRows - 1) / kTdRows;
+  const int H = n_branches + 1;
+  const size_t lds = ((size_t)H * 3 * kTdRows * n_actions + 2 * kTdRows * n_branches) * sizeof(float);
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute((const void*)td_loss_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return pbn::set_error(PBN_EDEVICE, "hipFuncSetAttribute failed");
+  hipLaunchKernelGGL(td_loss_kernel<true>, dim3(blocks), dim3(kTdThreads), lds, (hipStream_t)stream, d_online, d_target,
+                     d_actions, d_rewards, d_masks, batch, n_branches, n_actions, gamma, d_scratch, d_grad, d_weights,
+                     replay_constant, d_priority);
+  if (hipGetLastError() != hipSuccess) return pbn::set_error(PBN_EDEVICE, "td_loss_kernel launch failed");
+  // loss = sum_b w_b l_b / B (the rows' terms already carry 1 / K)
+  hipLaunchKernelGGL(td_loss_sum_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, d_scratch, blocks,
+                     1.f / (float)batch, d_loss);
   if (hipGetLastError() != hipSuccess) return pbn::set_error(PBN_EDEVICE, "td_loss_sum_kernel launch failed");
   return PBN_OK;
 }

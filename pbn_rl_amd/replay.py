@@ -22,6 +22,10 @@ double-DQN targets ``r + gamma * mask * Q_target(s', argmax_a Q(s', a))`` with t
 reference's ``mask = done`` (:109,122 -- it bootstraps only on done transitions; kept as is),
 MSE loss, gradients clamped to [-1, 1] (:129-130), one Adam step, and every
 ``target_update`` updates the target network moves halfway to the online one (:133-139).
+
+``PrioritisedDeviceReplay`` adds the other half of the reference's replay module,
+``PrioritisedER`` (bdq_model/memory.py:73-186): proportional prioritised replay over a sum and a
+min segment tree, held on the device (csrc/pbn_per.hip; DESIGN.md "Prioritised replay").
 """
 from __future__ import annotations
 
@@ -35,8 +39,8 @@ from . import _lib
 from .agent import BatchedBDQ, BranchingQNetwork
 from .vector_env import VectorPBNEnv
 
-__all__ = ["DeviceReplay", "bdq_update", "soft_update", "BDQLearner", "FusedBDQUpdate", "bdq_layout",
-           "fused_update_supported"]
+__all__ = ["DeviceReplay", "PrioritisedDeviceReplay", "bdq_update", "soft_update", "BDQLearner", "FusedBDQUpdate",
+           "bdq_layout", "fused_update_supported"]
 
 
 class DeviceReplay:
@@ -179,6 +183,126 @@ class DeviceReplay:
                 "rewards": rewards.reshape(-1, 1), "masks": masks.reshape(-1, 1)}
 
 
+class PrioritisedDeviceReplay(DeviceReplay):
+    """DeviceReplay with the reference's proportional priorities (PrioritisedER,
+    bdq_model/memory.py:73-186) in two device segment trees of ``tree_size`` leaves (the smallest
+    power of two >= capacity; double [2 * tree_size], node 1 the root, leaf i at tree_size + i):
+    ``sum_tree`` and ``min_tree``, plus ``max_priority`` (a one-element double, 1.0 at first).  GPU
+    only.  The law, quirks included (DESIGN.md "Prioritised replay"):
+
+    * ``store`` / ``store_at`` give the n new transitions the priority ``max_priority ** alpha``,
+      written at the slot AFTER each stored row (memory.py:114);
+    * ``sample(batch)`` draws ``batch`` (<= 1024) rows proportional to priority, one per stratum of
+      the total over leaves [0, size - 2], with the uniforms of the REPLAY Philox stream (seed, row,
+      draw counter), and returns the rows and their float32 importance weights
+      ``(N p_i) ** -beta / (N p_min) ** -beta``;
+    * beta lives on the device (``beta_t``; ``beta`` is the host's mirror) and every sample moves
+      it to ``min(max_beta, beta + beta_step)`` after reading it.  The reference's agent does this
+      once per env step (increment_beta, ddqn_per/__init__.py:488-523); here it happens once per
+      sample, so ``beta_step`` is per update;
+    * ``update_priorities(idx, priorities)`` sets leaf idx[b] to ``priorities[b] ** alpha`` (of equal
+      indices the highest b wins, as the reference's in-order loop has it), raises ``max_priority``
+      to the largest priority seen, and skips indices outside [0, size).
+
+    Every launch reads its counters from device memory, so all of it can be graph-captured."""
+
+    def __init__(self, capacity: int, words: int, branches: int, device, *, alpha: float = 0.6, beta: float = 0.4,
+                 max_beta: float = 1.0, beta_step: float = 0.0, seed: int = 0):
+        if torch.device(device).type != "cuda":
+            raise ValueError("PrioritisedDeviceReplay runs on the GPU")
+        if capacity < 2:
+            raise ValueError("capacity must be >= 2")
+        if not beta > 0:
+            raise ValueError("beta must be > 0")
+        super().__init__(capacity, words, branches, device)
+        dev = self.device
+        self.alpha = float(alpha)
+        self.tree_size = 1 << (self.capacity - 1).bit_length()
+        self.sum_tree = torch.zeros(2 * self.tree_size, dtype=torch.float64, device=dev)
+        self.min_tree = torch.full((2 * self.tree_size,), float("inf"), dtype=torch.float64, device=dev)
+        self.max_priority = torch.ones(1, dtype=torch.float64, device=dev)
+        self.beta, self.max_beta, self.beta_step = float(beta), float(max_beta), float(beta_step)
+        self.beta_t = torch.full((1,), self.beta, dtype=torch.float64, device=dev)
+        self.seed = int(seed)
+        self.counter_t = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def _i64(self, v: int) -> torch.Tensor:
+        return torch.full((1,), v, dtype=torch.int64, device=self.device)
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def clear(self) -> None:
+        """Empty the ring and the trees; max_priority back to 1 (PrioritisedER.clear)."""
+        self.pos = self.size = 0
+        self.sum_tree.zero_()
+        self.min_tree.fill_(float("inf"))
+        self.max_priority.fill_(1.0)
+
+    def store_priorities(self, n: int, pos_t: torch.Tensor) -> None:
+        """The priorities of n transitions stored at ring position ``*pos_t`` (the position before
+        the store; a one-element int64 device tensor): pbn_per_store, two launches."""
+        if not 1 <= n <= self.capacity:
+            raise ValueError("n must be in 1..capacity")
+        L = _lib.load()
+        with torch.cuda.device(self.device):
+            _lib.check(L.pbn_per_store(n, pos_t.data_ptr(), self.capacity, self.tree_size, self.alpha,
+                                       self.max_priority.data_ptr(), self.sum_tree.data_ptr(),
+                                       self.min_tree.data_ptr(), self._stream()), "pbn_per_store")
+
+    def store(self, state, target, action, reward, next_state, done) -> None:
+        self.store_priorities(target.shape[0], self._i64(self.pos))
+        super().store(state, target, action, reward, next_state, done)
+
+    def store_at(self, pos_t, size_t, state, target, *args, **kwargs) -> None:
+        self.store_priorities(target.shape[0], pos_t)       # (reads the position before it advances)
+        super().store_at(pos_t, size_t, state, target, *args, **kwargs)
+
+    def mirror_beta(self) -> None:
+        """The host's copy of beta after one sample (what a replayed graph's sample did)."""
+        self.beta = min(self.max_beta, self.beta + self.beta_step)
+
+    def sample(self, batch: int, size_t: Optional[torch.Tensor] = None):
+        """(rows int64 [batch], importance weights float32 [batch]): pbn_per_sample, one launch.
+        ``size_t`` (a one-element int64 device tensor) replaces the host fill level in
+        graph-captured frames."""
+        if not 1 <= batch <= 1024:
+            raise ValueError("batch must be in 1..1024")
+        if size_t is None:
+            if self.size < 2:
+                raise ValueError("prioritised sampling needs at least two stored transitions")
+            size_t = self._i64(self.size)
+        idx = torch.empty(batch, dtype=torch.int64, device=self.device)
+        weights = torch.empty(batch, dtype=torch.float32, device=self.device)
+        L = _lib.load()
+        with torch.cuda.device(self.device):
+            _lib.check(L.pbn_per_sample(batch, self.capacity, self.tree_size, size_t.data_ptr(),
+                                        self.sum_tree.data_ptr(), self.min_tree.data_ptr(), self.beta_t.data_ptr(),
+                                        self.max_beta, self.beta_step, self.seed, self.counter_t.data_ptr(),
+                                        idx.data_ptr(), weights.data_ptr(), self._stream()), "pbn_per_sample")
+        if not torch.cuda.is_current_stream_capturing():
+            self.mirror_beta()
+        return idx, weights
+
+    def update_priorities(self, idx: torch.Tensor, priorities: torch.Tensor,
+                          size_t: Optional[torch.Tensor] = None) -> None:
+        """pbn_per_update on (idx int64 [B], priorities float32 [B]), B <= 1024: one launch."""
+        if idx.dtype != torch.int64 or priorities.dtype != torch.float32 or idx.dim() != 1 or \
+                idx.shape != priorities.shape or not 1 <= idx.shape[0] <= 1024:
+            raise ValueError("idx int64 [B] and priorities float32 [B], B in 1..1024")
+        if not idx.is_cuda or not priorities.is_cuda:
+            raise ValueError("idx and priorities must be GPU tensors")
+        if size_t is None:
+            size_t = self._i64(self.size)
+        idx, priorities = idx.contiguous(), priorities.contiguous()
+        L = _lib.load()
+        with torch.cuda.device(self.device):
+            _lib.check(L.pbn_per_update(idx.shape[0], self.capacity, self.tree_size, self.alpha, size_t.data_ptr(),
+                                        idx.data_ptr(), priorities.data_ptr(), self.max_priority.data_ptr(),
+                                        self.sum_tree.data_ptr(), self.min_tree.data_ptr(), self._stream()),
+                       "pbn_per_update")
+
+
 @torch.no_grad()
 def soft_update(target: torch.nn.Module, online: torch.nn.Module) -> None:
     """target <- target / 2 + online / 2, parameter by parameter (bdq_model/__init__.py:137-139)."""
@@ -212,13 +336,54 @@ class _TDLoss(torch.autograd.Function):
         return grad * grad_out, None, None, None, None, None
 
 
+class _TDLossPER(torch.autograd.Function):
+    """pbn_bdq_td_loss_per: _TDLoss with per-row importance weights in and priorities out."""
+
+    @staticmethod
+    def forward(ctx, online, target_heads, actions, rewards, masks, weights, gamma, replay_constant, priorities_out):
+        H, rows, A = online.shape
+        B = rows // 2
+        loss = torch.empty(1, dtype=torch.float32, device=online.device)
+        grad = torch.empty_like(online)
+        scratch = torch.empty((B + 7) // 8, dtype=torch.float32, device=online.device)
+        L = _lib.load()
+        with torch.cuda.device(online.device):
+            _lib.check(L.pbn_bdq_td_loss_per(online.data_ptr(), target_heads.data_ptr(), actions.data_ptr(),
+                                             rewards.data_ptr(), masks.data_ptr(), weights.data_ptr(), B, H - 1, A,
+                                             float(gamma), float(replay_constant), loss.data_ptr(), grad.data_ptr(),
+                                             priorities_out.data_ptr(), scratch.data_ptr(),
+                                             torch.cuda.current_stream(online.device).cuda_stream),
+                       "pbn_bdq_td_loss_per")
+        ctx.save_for_backward(grad)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (grad,) = ctx.saved_tensors
+        return (grad * grad_out,) + (None,) * 8
+
+
 def bdq_update(q: torch.nn.Module, target: torch.nn.Module, opt: torch.optim.Optimizer, batch: Dict[str, torch.Tensor],
-               gamma: float = 0.999, grad_clamp: float = 1.0, target_weights=None) -> torch.Tensor:
+               gamma: float = 0.999, grad_clamp: float = 1.0, target_weights=None, weights: Optional[torch.Tensor] = None,
+               priorities_out: Optional[torch.Tensor] = None, replay_constant: float = 1e-5) -> torch.Tensor:
     """One update_policy step (bdq_model/__init__.py:111-131) on a gathered batch; returns the loss.
     On the GPU the duelings, the double-DQN target, the MSE and their backward run as one HIP
     launch on the raw head outputs (``pbn_bdq_td_loss``); elsewhere (CPU tensors) as PyTorch
     expressions.  ``target_weights``: the target network's ``head_weights()`` computed beforehand
-    (it changes only at soft updates)."""
+    (it changes only at soft updates).
+
+    ``weights`` (float32 [B]; prioritised replay's importance weights): the update of
+    DDQNPER._learn_step (ddqn_per/__init__.py:468-483) with this MSE: l_b = mean_k (y_bk - q_bk)^2,
+    loss = mean_b w_b l_b, and ``priorities_out`` (float32 [B], optional) receives
+    |w_b l_b| + ``replay_constant``.  On the GPU this is ``pbn_bdq_td_loss_per``."""
+    if weights is None and priorities_out is not None:
+        raise ValueError("priorities_out needs weights")
+    if weights is not None:
+        if weights.dtype != torch.float32 or weights.numel() != batch["obs"].shape[1]:
+            raise ValueError("weights must be float32 [B]")
+        if priorities_out is not None and (priorities_out.dtype != torch.float32 or priorities_out.shape != (weights.numel(),)
+                                           or not priorities_out.is_contiguous()):
+            raise ValueError("priorities_out must be a contiguous float32 [B]")
     # q(obs) and q(next_obs) as one forward over 2B rows (half the launches; only the first
     # half carries gradient)
     B = batch["obs"].shape[1]
@@ -228,8 +393,15 @@ def bdq_update(q: torch.nn.Module, target: torch.nn.Module, opt: torch.optim.Opt
         with torch.no_grad():
             t_heads = target.forward_heads(target.model[0](batch["next_obs"]),
                                            weights=target_weights).contiguous()   # (K+1, B, A)
-        loss = _TDLoss.apply(heads.contiguous(), t_heads, batch["actions"].reshape(B, -1).contiguous(),
-                             batch["rewards"].reshape(B).contiguous(), batch["masks"].reshape(B).contiguous(), gamma)
+        if weights is None:
+            loss = _TDLoss.apply(heads.contiguous(), t_heads, batch["actions"].reshape(B, -1).contiguous(),
+                                 batch["rewards"].reshape(B).contiguous(), batch["masks"].reshape(B).contiguous(), gamma)
+        else:
+            if priorities_out is None:
+                priorities_out = torch.empty(B, dtype=torch.float32, device=x.device)
+            loss = _TDLossPER.apply(heads.contiguous(), t_heads, batch["actions"].reshape(B, -1).contiguous(),
+                                    batch["rewards"].reshape(B).contiguous(), batch["masks"].reshape(B).contiguous(),
+                                    weights.reshape(B).contiguous(), gamma, replay_constant, priorities_out)
     else:
         q_all = q(x)                                                    # (2B, K, A)
         current = q_all[:B].gather(2, batch["actions"]).squeeze(-1)     # (B, K)
@@ -237,7 +409,13 @@ def bdq_update(q: torch.nn.Module, target: torch.nn.Module, opt: torch.optim.Opt
             argmax = torch.argmax(q_all[B:].detach(), dim=2)
             max_next = target(batch["next_obs"]).gather(2, argmax.unsqueeze(2)).squeeze(-1)
         expected = batch["rewards"] + max_next * gamma * batch["masks"]
-        loss = F.mse_loss(expected, current)
+        if weights is None:
+            loss = F.mse_loss(expected, current)
+        else:
+            sq = (expected - current) ** 2                              # (B, K)
+            loss = (weights.reshape(B, 1) * sq).mean()                  # = mean_b w_b l_b
+            if priorities_out is not None:
+                priorities_out.copy_((weights.reshape(B) * sq.detach().mean(1)).abs() + replay_constant)
     opt.zero_grad()
     loss.backward()
     grads = [p.grad for p in q.parameters() if p.grad is not None]
@@ -447,15 +625,32 @@ class BDQLearner:
     ``fused`` (default: whenever the network is the reference's BranchingQNetwork on the GPU and
     the batch is a multiple of 16) runs each update as FusedBDQUpdate's three HIP launches; the
     Adam state is then FusedBDQUpdate's and ``opt`` is None.  ``fused=False`` keeps the PyTorch
-    update (bdq_update + torch.optim.Adam)."""
+    update (bdq_update + torch.optim.Adam).
+
+    ``prioritised=True`` (GPU only) trains from a PrioritisedDeviceReplay as DDQNPER does
+    (ddqn_per/__init__.py:468-483): every update is sample -> gather -> importance-weighted
+    bdq_update -> update_priorities with |w_b l_b| + ``replay_constant``.  It uses the PyTorch
+    update (``fused=True`` with it raises: the fused update takes no weights).  ``per_beta`` moves
+    to ``per_max_beta`` in ``per_beta_steps`` equal steps, one per update; ``capture()`` works
+    with it, the host mirroring beta as it mirrors epsilon."""
 
     def __init__(self, env: VectorPBNEnv, qnet: Optional[BranchingQNetwork] = None, *, capacity: int = 10 ** 4,
                  batch_size: int = 256, learning_rate: float = 1e-4, gamma: float = 0.999,
                  target_update: int = 10_000, learning_starts: int = 288, updates_per_frame: int = 1,
                  epsilon_start: float = 1.0, epsilon_final: float = 0.0, epsilon_decay: int = 10_000, seed: int = 0,
-                 graphable: bool = False, blas: Optional[str] = "cublas", fused: Optional[bool] = None):
+                 graphable: bool = False, blas: Optional[str] = "cublas", fused: Optional[bool] = None,
+                 prioritised: bool = False, per_alpha: float = 0.6, per_beta: float = 0.4, per_max_beta: float = 1.0,
+                 per_beta_steps: int = 10_000, replay_constant: float = 1e-5):
+        if prioritised:   # (contradictory arguments: refused before the env is looked at)
+            if fused:
+                raise ValueError("prioritised replay uses the PyTorch update: fused=True takes no importance weights")
+            if batch_size > 1024:
+                raise ValueError("prioritised replay samples at most 1024 rows per update")
+            fused = False
         if not env.keep_final_state:
             raise ValueError("BDQLearner needs the env's final_state (keep_final_state=True)")
+        self.prioritised = bool(prioritised)
+        self.replay_constant = float(replay_constant)
         self.env = env
         self.agent = BatchedBDQ(env, qnet)
         self.q = self.agent.q.train()
@@ -482,7 +677,13 @@ class BDQLearner:
             # one fused multi-tensor kernel per step instead of a handful per parameter tensor
             # capturable keeps Adam's step counts on the device (needed to replay it in a hipGraph)
             self.opt = torch.optim.Adam(self.q.parameters(), lr=learning_rate, fused=True, capturable=graphable)
-        self.replay = DeviceReplay(max(capacity, env.n_alloc), env.words, self.agent.branches, env.device)
+        if prioritised:
+            self.replay = PrioritisedDeviceReplay(
+                max(capacity, env.n_alloc), env.words, self.agent.branches, env.device, alpha=per_alpha, beta=per_beta,
+                max_beta=per_max_beta, beta_step=(per_max_beta - per_beta) / max(1, per_beta_steps), seed=seed)
+            self._prio = torch.empty(batch_size, dtype=torch.float32, device=env.device)
+        else:
+            self.replay = DeviceReplay(max(capacity, env.n_alloc), env.words, self.agent.branches, env.device)
         self.batch_size, self.gamma, self.target_update = batch_size, gamma, target_update
         self.learning_starts = max(learning_starts, batch_size)
         self.updates_per_frame = updates_per_frame
@@ -547,6 +748,8 @@ class BDQLearner:
             for u in range(self.updates_per_frame):
                 if self.fused is not None:
                     self.last_loss = self.fused.update(self.replay, self._idx[u * self.batch_size:(u + 1) * self.batch_size])
+                elif self.prioritised:
+                    self.last_loss = self._update_prioritised()
                 else:
                     self.last_loss = self._update(self.replay.sample_indices(self.batch_size, self.gen))
                 self.updates += 1
@@ -569,6 +772,16 @@ class BDQLearner:
             return self.fused.update(self.replay, idx)
         batch = self.replay.gather(idx, self.env.net)
         return bdq_update(self.q, self.target, self.opt, batch, self.gamma, target_weights=self._target_weights())
+
+    def _update_prioritised(self, size_t: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """sample -> gather -> weighted update -> update_priorities (DDQNPER._learn_step)."""
+        rp = self.replay
+        idx, w = rp.sample(self.batch_size, size_t)
+        batch = rp.gather(idx, self.env.net)
+        loss = bdq_update(self.q, self.target, self.opt, batch, self.gamma, target_weights=self._target_weights(),
+                          weights=w, priorities_out=self._prio, replay_constant=self.replay_constant)
+        rp.update_priorities(idx, self._prio, size_t)
+        return loss
 
     def _soft_update(self) -> None:
         if self.fused is not None:
@@ -644,6 +857,8 @@ class BDQLearner:
         if self._ring is not None:
             # one launch: the step, in place, writing its transitions into the ring
             env.step_flipmask_dev_store(self._step_t, self._ring)
+            if self.prioritised:   # (the new rows' priorities; the position advances below)
+                self.replay.store_priorities(env.n_alloc, self._pos_t)
         else:
             env.step_flipmask_dev(self._step_t, copy_back=False)
             # the ring store reads the pre-step state (still in env.state) and target (carried in
@@ -673,6 +888,8 @@ class BDQLearner:
             if fused:
                 loss = self.fused.update(self.replay, self._idx[u * B:(u + 1) * B],
                                          advance=self._adv if u == U - 1 else None)
+            elif self.prioritised:
+                loss = self._update_prioritised(self._size_t)
             else:
                 loss = self._update(self.replay.sample_indices(B, self.gen, size_t=self._size_t))
         return env.reward[: env.num_envs], self._done_buf[: env.num_envs].view(torch.bool), loss
@@ -694,6 +911,9 @@ class BDQLearner:
         rp.pos = (rp.pos + env.n_alloc) % rp.capacity
         rp.size = min(rp.size + env.n_alloc, rp.capacity)
         self.epsilon = max(self.epsilon_final, self.epsilon - self.epsilon_step)
+        if self.prioritised:
+            for _ in range(self.updates_per_frame):
+                rp.mirror_beta()
         self.frames += 1
         self.updates += self.updates_per_frame
         if self.updates % self.target_update == 0:

@@ -1,0 +1,279 @@
+"""Prioritised replay on the GPU (csrc/pbn_per.hip, pbn_bdq_td_loss_per, PrioritisedDeviceReplay,
+BDQLearner(prioritised=True)) against the numpy restatement of the law (tests/per_oracle.py, itself
+pinned to the reference's PrioritisedER by tests/test_per_host.py).
+
+Comparison method: after every device operation the leaves of both trees are read back and must be
+within 16 fp64 ulp of the oracle's ``p ** alpha`` (OpenCL's bound for pow; the documentation shipped
+with the ROCm device library states no tighter one); the oracle then adopts the device's leaves and is
+rebuilt, and every internal node of both trees, and max_priority, must equal it bit for bit."""
+import numpy as np
+import pytest
+import torch
+
+from pbn_rl_amd.agent import BranchingQNetwork
+from pbn_rl_amd.attractors import load_attractors
+from pbn_rl_amd.network import load_network
+from pbn_rl_amd.replay import BDQLearner, PrioritisedDeviceReplay, _TDLoss, _TDLossPER
+from pbn_rl_amd.spec import EnvSpec
+from pbn_rl_amd.vector_env import VectorPBNEnv
+
+from .per_oracle import PerOracle, replay_uniforms, ulp_distance
+
+pytestmark = pytest.mark.gpu
+
+ALPHA = 0.6
+POW_ULP = 16
+SEED = 99
+
+
+def make(cap, **kw):
+    rp = PrioritisedDeviceReplay(cap, 1, 1, torch.device("cuda"), alpha=ALPHA, seed=SEED, **kw)
+    return rp, PerOracle(cap, ALPHA)
+
+
+def check_trees(rp, o, what):
+    """The comparison method of the module docstring; returns the largest leaf distance in ulp."""
+    torch.cuda.synchronize()
+    T = o.T
+    s, m = rp.sum_tree.cpu().numpy(), rp.min_tree.cpu().numpy()
+    d = max(int(ulp_distance(s[T:], o.sum_leaves()).max()), int(ulp_distance(m[T:], o.min_leaves()).max()))
+    print(f"{what}: largest leaf distance {d} ulp")
+    assert d <= POW_ULP, what
+    o.adopt_leaves(s[T:], m[T:])
+    assert np.array_equal(s[1:T].view(np.int64), o.sum[1:T].view(np.int64)), what
+    assert np.array_equal(m[1:T].view(np.int64), o.min[1:T].view(np.int64)), what
+    assert float(rp.max_priority) == o.max_priority, what
+    return d
+
+
+def dev_store(rp, o, n):
+    rp.store_priorities(n, torch.tensor([rp.pos], dtype=torch.int64, device=rp.device))
+    rp.pos = (rp.pos + n) % rp.capacity
+    rp.size = min(rp.size + n, rp.capacity)
+    o.store(n)
+    assert (rp.pos, rp.size) == (o.pos, o.size)
+
+
+def dev_update(rp, o, idx, prio):
+    rp.update_priorities(torch.from_numpy(idx).cuda(), torch.from_numpy(prio).cuda())
+    return o.update(idx, prio)
+
+
+def dev_sample(rp, o, B):
+    """One device sample against the oracle (whose trees equal the device's bit for bit after
+    check_trees): rows exactly, weights within 1 fp32 ulp, beta and the counter advanced."""
+    beta, ctr = float(rp.beta_t), int(rp.counter_t)
+    assert beta == rp.beta
+    idx, w = rp.sample(B)
+    torch.cuda.synchronize()
+    want_idx, want_w = o.sample(B, beta, replay_uniforms(SEED, ctr, B))
+    assert np.array_equal(idx.cpu().numpy(), want_idx)
+    assert int(idx.min()) >= 0 and int(idx.max()) < rp.size
+    d = int(ulp_distance(w.cpu().numpy(), want_w).max())
+    print(f"sample B={B} size={rp.size}: largest weight distance {d} fp32 ulp")
+    assert d <= 1
+    assert int(rp.counter_t) == ctr + 1
+    assert float(rp.beta_t) == min(rp.max_beta, beta + rp.beta_step) == rp.beta
+    return idx, w
+
+
+def random_update(rng, o, B, top):
+    idx = rng.integers(0, o.size, size=B).astype(np.int64)
+    prio = (rng.random(B) * top + 1e-4).astype(np.float32)
+    return idx, prio
+
+
+@pytest.mark.parametrize("cap,pos,n", [(1000, 990, 40), (5000, 3000, 4096), (1024, 0, 1024),
+                                       (1 << 20, 1_040_000, 32768)])
+def test_store(cap, pos, n):
+    """A whole-ring store into empty trees (priority 1.0 ** alpha, exactly 1.0), an update that
+    raises max_priority, then the case's store at ``pos`` with the grown priority: ranges that
+    wrap, start and end inside a chunk, cover the whole tree, and touch 65 chunks of a 2^20 tree."""
+    rp, o = make(cap)
+    rng = np.random.default_rng(cap)
+    dev_store(rp, o, cap)
+    assert check_trees(rp, o, "fill") == 0 and float(rp.sum_tree[1]) == float(cap)
+    idx, prio = random_update(rng, o, 1000, 50.0)
+    dev_update(rp, o, idx, prio)
+    check_trees(rp, o, "update")
+    assert o.max_priority > 40.0
+    rp.pos = o.pos = pos
+    dev_store(rp, o, n)
+    check_trees(rp, o, f"store {cap} {pos} {n}")
+    leaves = (pos + 1 + np.arange(n)) % cap
+    assert len(np.unique(rp.sum_tree[o.T + torch.from_numpy(leaves).cuda()].cpu().numpy())) == 1
+
+
+@pytest.mark.parametrize("B", [32, 256, 1000])
+def test_sample(B):
+    """Below capacity (3,000 of 5,000 rows) and at capacity (after a wrap), over varied
+    priorities; then the same launch captured in a graph and replayed draws the same rows."""
+    rp, o = make(5000, beta=0.4, max_beta=0.5, beta_step=0.04)
+    rng = np.random.default_rng(B)
+    dev_store(rp, o, 3000)
+    dev_update(rp, o, *random_update(rng, o, 1000, 8.0))
+    check_trees(rp, o, "below capacity")
+    dev_sample(rp, o, B)
+    dev_sample(rp, o, B)
+    dev_store(rp, o, 2500)
+    dev_update(rp, o, *random_update(rng, o, 1000, 8.0))
+    check_trees(rp, o, "at capacity")
+    assert rp.size == 5000
+    dev_sample(rp, o, B)                       # (beta reaches max_beta here)
+    beta0, ctr0 = rp.beta_t.clone(), rp.counter_t.clone()
+    idx_e, w_e = dev_sample(rp, o, B)
+    rp.beta_t.copy_(beta0)
+    rp.counter_t.copy_(ctr0)
+    size_t = torch.tensor([rp.size], dtype=torch.int64, device=rp.device)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        idx_g, w_g = rp.sample(B, size_t)
+    g.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(idx_e, idx_g) and torch.equal(w_e, w_g)
+    assert int(rp.counter_t) == int(ctr0) + 1
+
+
+def test_update_chain():
+    """Three chained rounds of store, sample and update on a 1,000-row ring that wraps in the third:
+    the update takes the sampled rows with forced duplicates (positions 3 and 7 get position 1's
+    row; the highest position wins), one index past the fill level and one negative (both
+    skipped), and random fp32 priorities."""
+    rp, o = make(1000, beta=0.4, beta_step=0.1)
+    rng = np.random.default_rng(5)
+    B = 256
+    for r in range(3):
+        dev_store(rp, o, 400)
+        check_trees(rp, o, f"round {r} store")
+        idx, _ = dev_sample(rp, o, B)
+        idx = idx.cpu().numpy().copy()
+        idx[3] = idx[7] = idx[1]
+        idx[5] = o.size if o.size < 1000 else 1000 + r
+        idx[9] = -1
+        prio = (rng.random(B) * (4.0 + 4.0 * r) + 1e-4).astype(np.float32)
+        prio[5] = prio[9] = 1e6               # skipped pairs: max_priority must not see them
+        prio[3] = np.float32(20.0 + r)        # a duplicate that loses its leaf still counts
+        ok = dev_update(rp, o, idx, prio)
+        assert not ok[5] and not ok[9] and ok.sum() == B - 2
+        check_trees(rp, o, f"round {r} update")
+        assert o.max_priority == 20.0 + r
+    assert rp.pos == 200 and rp.size == 1000
+    rp.clear()
+    torch.cuda.synchronize()
+    assert rp.size == 0 and float(rp.sum_tree.sum()) == 0.0 and bool(torch.isinf(rp.min_tree).all())
+    assert float(rp.max_priority) == 1.0
+
+
+@pytest.mark.parametrize("B,K", [(256, 3), (512, 3), (32, 1), (40, 7)])
+def test_td_loss_per_matches_pytorch(B, K):
+    """pbn_bdq_td_loss_per against the same update written in PyTorch (test_gpu_replay.py's
+    test_fused_td_loss_matches_pytorch with random importance weights): the loss and the
+    priorities to rtol 1e-5, every parameter gradient to rtol 1e-4 / atol 1e-7; and with weights
+    of 1, loss and gradients equal pbn_bdq_td_loss's to the same tolerances."""
+    import copy
+    torch.manual_seed(3)
+    N = 28
+    q = BranchingQNetwork((N, N), N + 1, K).cuda()
+    tgt = copy.deepcopy(q)
+    with torch.no_grad():
+        for p in tgt.parameters():
+            p.add_(0.01 * torch.randn_like(p))
+    g = torch.Generator(device="cuda").manual_seed(5)
+    obs = torch.randint(0, 2, (2, B, N), device="cuda", generator=g).float()
+    nxt = torch.randint(0, 2, (2, B, N), device="cuda", generator=g).float()
+    actions = torch.randint(0, N + 1, (B, K, 1), device="cuda", generator=g)
+    rewards = torch.randn(B, 1, device="cuda", generator=g)
+    masks = torch.randint(0, 2, (B, 1), device="cuda", generator=g).float()
+    w = torch.rand(B, device="cuda", generator=g) + 0.05
+    rc = 1e-5
+    x = torch.cat([obs, nxt], 1)
+    params = list(q.parameters())
+
+    def fused(weights):
+        heads = q.forward_heads(q.model[0](x))
+        with torch.no_grad():
+            t_heads = tgt.forward_heads(tgt.model[0](nxt)).contiguous()
+        a = (heads.contiguous(), t_heads, actions.reshape(B, K).contiguous(), rewards.reshape(B).contiguous(),
+             masks.reshape(B).contiguous())
+        if weights is None:
+            return _TDLoss.apply(*a, 0.9), None
+        prio = torch.full((B,), -1.0, device="cuda")
+        return _TDLossPER.apply(*a, weights, 0.9, rc, prio), prio
+
+    def same(ga, gb):
+        for a, b in zip(ga, gb):
+            if a is None or b is None:
+                assert a is None and b is None
+                continue
+            assert torch.allclose(a, b, rtol=1e-4, atol=1e-7), (a - b).abs().max().item()
+
+    loss_f, prio_f = fused(w)
+    g_f = torch.autograd.grad(loss_f, params, allow_unused=True)
+    q_all = q(x)
+    cur = q_all[:B].gather(2, actions).squeeze(-1)
+    with torch.no_grad():
+        am = q_all[B:].argmax(dim=2)
+        mx = tgt(nxt).gather(2, am.unsqueeze(2)).squeeze(-1)
+    lb = ((rewards + mx * 0.9 * masks - cur) ** 2).mean(1)
+    loss_t = (w * lb).mean()
+    g_t = torch.autograd.grad(loss_t, params, allow_unused=True)
+    assert torch.allclose(loss_f, loss_t, rtol=1e-5, atol=0), (loss_f.item(), loss_t.item())
+    assert torch.allclose(prio_f, (w * lb.detach()).abs() + rc, rtol=1e-5, atol=0)
+    same(g_f, g_t)
+    loss_1, prio_1 = fused(torch.ones(B, device="cuda"))
+    loss_0, _ = fused(None)
+    assert torch.allclose(loss_1, loss_0, rtol=1e-5, atol=0)
+    same(torch.autograd.grad(loss_1, params, allow_unused=True), torch.autograd.grad(loss_0, params, allow_unused=True))
+    assert torch.allclose(prio_1.mean() - rc, loss_0, rtol=1e-4)
+
+
+def _learner(n, seed):
+    spec = EnvSpec(load_network("pbn28"), load_attractors("pbn28"), perturbation=0.01)
+    env = VectorPBNEnv(spec, n, seed=seed)
+    torch.manual_seed(4)
+    lr = BDQLearner(env, BranchingQNetwork((28, 28), 29, 3), capacity=8 * n, learning_starts=2 * n, batch_size=256,
+                    target_update=4, epsilon_start=1.0, epsilon_final=1.0, seed=11, graphable=True, fused=False,
+                    prioritised=True, per_beta=0.4, per_beta_steps=20)
+    env.reset()
+    return env, lr
+
+
+def _tree_invariant(rp):
+    T = rp.tree_size
+    s, m = rp.sum_tree.cpu().numpy(), rp.min_tree.cpu().numpy()
+    assert np.array_equal(s[1:T], s[2:2 * T:2] + s[3:2 * T:2])
+    assert np.array_equal(m[1:T], np.minimum(m[2:2 * T:2], m[3:2 * T:2]))
+    return s[1]
+
+
+def test_prioritised_learner_eager_and_captured():
+    """pbn28, 1,024 envs, batch 256, twelve frames at epsilon = 1 (the actions do not depend on Q):
+    the eager and the captured learner agree exactly on env state, ring, position, fill level and
+    beta; on both, every internal tree node equals the operation of its children; the sum roots
+    agree to 1e-3 (the losses carry GEMM rounding into the leaves)."""
+    n = 1024
+    env_e, eager = _learner(n, 21)
+    env_g, graph = _learner(n, 21)
+    assert isinstance(graph.replay, PrioritisedDeviceReplay) and graph.fused is None
+    graph.capture()
+    assert graph.updates == 3 and graph.frames == 4
+    for _ in range(graph.frames):
+        eager.frame()
+    for k in range(8):
+        re, de = eager.frame()
+        rg, dg = graph.frame()
+        torch.cuda.synchronize()
+        assert torch.equal(re, rg) and torch.equal(de, dg), k
+        assert torch.equal(env_e.state, env_g.state), k
+    assert graph.frames == eager.frames == 12 and graph.updates == eager.updates == 11
+    R, S = eager.replay, graph.replay
+    assert R.pos == S.pos == int(graph._pos_t.item()) and R.size == S.size == int(graph._size_t.item())
+    for f in ("state", "next_state", "target", "action", "reward", "done"):
+        assert torch.equal(getattr(R, f), getattr(S, f)), f
+    assert R.beta == S.beta == float(R.beta_t) == float(S.beta_t) and R.beta > 0.4
+    assert int(R.counter_t) == int(S.counter_t) == 11
+    root_e, root_g = _tree_invariant(R), _tree_invariant(S)
+    assert abs(root_e - root_g) <= 1e-3 * abs(root_e), (root_e, root_g)
+    assert float(R.max_priority) >= 1.0 and float(S.max_priority) >= 1.0
+    assert torch.isfinite(graph.last_loss) and torch.isfinite(eager.last_loss)
