@@ -573,6 +573,33 @@ int pbn_bdq_learn(const pbn_net* net, int64_t batch, const int64_t* d_idx, int64
                   const pbn_frame_advance* advance, void* stream);
 
 /*
+ * pbn_bdq_learn_per: pbn_bdq_learn on a batch drawn by prioritised replay (pbn_per_sample), the
+ * update of DDQNPER._learn_step (ddqn_per/__init__.py:468-483) with this MSE.  An additive export
+ * (the ABI version is unchanged).  Every argument up to d_grad is pbn_bdq_learn's; then
+ *   d_weights   in  float [B]  the rows' importance weights, by batch position (d_weights[b] belongs
+ *                              to d_idx[b]; a batch may hold one ring row twice)
+ *   d_priority  out float [B]  the rows' new priorities, by batch position (for pbn_per_update)
+ * both required and 4-byte aligned.  In fp32, with d_bk = expected - current of row b, branch k:
+ *   g_bk        = (2 (current - expected) / (B K)) * w_b   the gradient at the head outputs: the
+ *                 unweighted value times w_b, so unit weights give pbn_bdq_learn's gradient, Adam
+ *                 step and image bit for bit
+ *   l_b         = (sum_k d_bk^2, k ascending) / K
+ *   priority[b] = |w_b l_b| + replay_constant
+ *   loss        = (sum_b w_b l_b) / B, the rows added in a fixed order (16-row blocks, then the
+ *                 blocks in order)
+ * The same three launches: the priorities are written by the backward's TD pass.  Rejects what
+ * pbn_bdq_learn rejects, and a null or misaligned d_weights / d_priority.
+ */
+int pbn_bdq_learn_per(const pbn_net* net, int64_t batch, const int64_t* d_idx, int64_t capacity,
+                      const uint32_t* d_state, const uint32_t* d_next_state, const uint8_t* d_target,
+                      const int32_t* d_action, int32_t n_branches, const float* d_reward, const uint8_t* d_done,
+                      float* d_params, float* d_Tq, const float* d_target_params, const float* d_target_Tq,
+                      float* d_adam_m, float* d_adam_v, float* d_adam_step, float lr, float beta1, float beta2,
+                      float eps, float gamma, float grad_clamp, float slope, void* d_workspace, int64_t workspace_bytes,
+                      float* d_loss, float* d_grad, const float* d_weights, float replay_constant, float* d_priority,
+                      const pbn_frame_advance* advance, void* stream);
+
+/*
  * pbn_copy_async (ABI 7): d_dst[0 .. bytes) <- d_src[0 .. bytes), device to device on `stream`:
  * one kernel of 16-byte non-temporal loads and stores (the world-1 hand-off of a rollout's
  * transition records, pbn_rl_amd/distributed.py; hipMemcpyAsync's blit ran 22 MB at 3.9 TB/s,

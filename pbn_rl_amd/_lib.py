@@ -31,7 +31,7 @@ EXPORTS = ["pbn_net_create", "pbn_net_destroy", "pbn_net_words", "pbn_reset", "p
            "pbn_qnet_flipmask_from_state", "pbn_replay_store", "pbn_replay_advance", "pbn_replay_batch", "pbn_bdq_td_loss", "pbn_bdq_layout", "pbn_bdq_learn_workspace",
            "pbn_bdq_pack", "pbn_bdq_image_floats", "pbn_bdq_learn", "pbn_copy_async", "pbn_rollout_copy", "pbn_host_buffer", "pbn_host_buffer_free", "pbn_stream_sync",
            "pbn_eval_track", "pbn_eval_reduce", "pbn_per_store", "pbn_per_sample", "pbn_per_update",
-           "pbn_bdq_td_loss_per", "pbn_last_error", "pbn_abi_version"]
+           "pbn_bdq_td_loss_per", "pbn_bdq_learn_per", "pbn_last_error", "pbn_abi_version"]
 SOURCES = ["pbn_env.hip", "pbn_settle.hip", "pbn_agent.hip", "pbn_qnet.hip", "pbn_learn.hip", "pbn_eval.hip",
            "pbn_per.hip"]
 
@@ -200,6 +200,10 @@ def load() -> ctypes.CDLL:
         L.pbn_per_update.restype = ctypes.c_int
         L.pbn_bdq_td_loss_per.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp]
         L.pbn_bdq_td_loss_per.restype = ctypes.c_int
+    if hasattr(L, "pbn_bdq_learn_per"):   # (additive export of ABI 11: the fused update on a prioritised batch)
+        L.pbn_bdq_learn_per.argtypes = ([vp, i64, vp, i64, vp, vp, vp, vp, i32, vp, vp] + [vp] * 7 + [f32] * 7 +
+                                        [vp, i64, vp, vp, vp, f32, vp, vp, vp])
+        L.pbn_bdq_learn_per.restype = ctypes.c_int
     L.pbn_abi_version.argtypes = []
     L.pbn_abi_version.restype = ctypes.c_int
     _lib = L

@@ -18,7 +18,9 @@
 //                the online argmax over s', the target network's value there, the MSE's partial
 //                sum, and the gradient at the head outputs; then the backward through the heads
 //                and the trunk (transposed MFMA tiles, LeakyReLU derivative from the stored
-//                activation), storing every layer's delta.
+//                activation), storing every layer's delta.  With importance weights
+//                (pbn_bdq_learn_per, the <true> instantiation) the TD pass scales each row's
+//                gradient by its weight and writes the row's priority.
 //   learn_apply  one wave per 16 x 16 gradient tile (K = the batch: dW = delta . act^T), the
 //                bilinear layer's weight gradient from the packed state and target bits
 //                (dW[o][i][j] = sum_r g[o][r] s_i[r] t_j[r]); each wave clamps its tile to
@@ -144,6 +146,11 @@ struct LearnArgs {
   float* partial; // [B / 16]
   float* loss;
   float* grad;    // optional: the clamped gradient, parameter layout
+  // prioritised replay (pbn_bdq_learn_per; learn_bwd_kernel<true>): the rows' importance weights
+  // in, their priorities out, both by batch position; null / 0 otherwise
+  const float* wts;   // [B]
+  float* prio;        // [B]
+  float rconst;
   unsigned long long* stamps;   // diagnostic builds (PBN_STAMPS): [kernel][block][wave][32] s_memtime
   // the frame's counters and the next frame's rows (pbn_frame_advance): learn_apply's extra last
   // block, when adv_on
@@ -506,6 +513,13 @@ __device__ __forceinline__ float wave_sum(float x) {
   return x;
 }
 
+// kPer (pbn_bdq_learn_per): the TD pass is td_loss_kernel<true>'s (pbn_agent.hip).  Batch row b
+// carries an importance weight w_b, read by batch position (a batch may hold a ring row twice):
+// l_b = (sum_k (expected - current)^2, k ascending) / K, g is the unweighted g times w_b,
+// priority[b] = |w_b l_b| + replay_constant, and the block's partial is the sum of its w_b l_b
+// (learn_apply divides the total by B: loss = mean_b w_b l_b).  Everything after the pass is the
+// same code; without kPer the kernel is the unweighted one, expression for expression.
+template <bool kPer>
 __global__ void __launch_bounds__(kThreads) learn_bwd_kernel(LearnArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int H = a.H, A = a.A, Ap = a.Apad, K = a.K, B = a.B;
@@ -558,11 +572,12 @@ __global__ void __launch_bounds__(kThreads) learn_bwd_kernel(LearnArgs a) {
 #pragma unroll
   for (int k = 0; k < kHeadPre; ++k) hv[k] = head_src(min(tid + kThreads * k, n4 - 1));
   int ak = 0;
-  float rwj = 0.f, dnj = 0.f;
+  float rwj = 0.f, dnj = 0.f, wj = 1.f;
   if (tdl) {
     ak = a.act[(size_t)jrow * K + (tp >> 4)];
     rwj = a.rew[jrow];
     dnj = (float)a.done[jrow];
+    if constexpr (kPer) wj = a.wts[b0 + (tp & 15)];   // (with the pass's other operands: issue order above)
   }
   if (wrow) {
     const int b = b0 + tid - 64 * (kWaves - 1);
@@ -671,7 +686,8 @@ __global__ void __launch_bounds__(kThreads) learn_bwd_kernel(LearnArgs a) {
       const float expected = rwj + (tnext * a.gamma) * dnj;
       const float d = expected - current;
       sd[r * K + k] = d * d;
-      sg[r * K + k] = 2.f * (current - expected) / (float)(B * K);
+      const float gk = 2.f * (current - expected) / (float)(B * K);
+      sg[r * K + k] = kPer ? gk * wj : gk;
       sact[r * K + k] = ak;
     }
   }
@@ -698,7 +714,19 @@ __global__ void __launch_bounds__(kThreads) learn_bwd_kernel(LearnArgs a) {
   }
   if (wave == 0) {   // the block's squared TD errors, a fixed-order reduction
     float sacc = 0.f;
-    for (int p = lane; p < kRows * K; p += 64) sacc += sd[p];
+    if constexpr (kPer) {
+      // lane r < 16: row r's weighted loss and priority.  Row r's weight is in lane 4 r of this
+      // wave (pair p = r: branch 0 of row r; 4 * 16 * K >= 64, so those lanes ran the pass)
+      const float wr = __shfl(wj, 4 * rr);
+      if (lane < kRows) {
+        float l = 0.f;
+        for (int k = 0; k < K; ++k) l += sd[lane * K + k];
+        sacc = wr * (l / (float)K);
+        a.prio[b0 + lane] = fabsf(sacc) + a.rconst;
+      }
+    } else {
+      for (int p = lane; p < kRows * K; p += 64) sacc += sd[p];
+    }
     sacc = wave_sum(sacc);
     if (lane == 0) {
       a.partial[tile] = sacc;
@@ -847,7 +875,7 @@ __global__ void __launch_bounds__(64 * kApplyWaves) learn_apply_kernel(LearnArgs
     for (int p = lane; p < B / kRows; p += 64) s += a.partial[p];
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
-    if (lane == 0) a.loss[0] = s / (float)(B * a.K);
+    if (lane == 0) a.loss[0] = s / (float)(a.wts ? B : B * a.K);   // (weighted: mean_b w_b l_b, l_b the mean over k)
   }
   const float stepc = a.step[0];
   const float bc1 = 1.f - powf(a.b1, stepc);
@@ -1146,9 +1174,19 @@ size_t learn_bwd_lds(int H, int Apad, int K) {
   return (std::max(planes, staged) + 3 * kRows * K) * sizeof(float);
 }
 
+int check_branches(int n_branches) {
+  if (n_branches < 1 || n_branches > 7) return pbn::set_error(PBN_EINVAL, "fused BDQ update: n_branches 1..7");
+  return PBN_OK;
+}
+
 int check_shape(int N, int n_branches) {
   if (N < 1 || N > 127) return pbn::set_error(PBN_EINVAL, "fused BDQ update: 1 <= n_nodes <= 127");
-  if (n_branches < 1 || n_branches > 7) return pbn::set_error(PBN_EINVAL, "fused BDQ update: n_branches 1..7");
+  return check_branches(n_branches);
+}
+
+int check_batch(int64_t batch) {
+  if (batch < kRows || batch % kRows || batch > (1 << 20))
+    return pbn::set_error(PBN_EINVAL, "fused BDQ update: batch a multiple of 16, 16..2^20");
   return PBN_OK;
 }
 
@@ -1177,8 +1215,7 @@ int pbn_bdq_learn_workspace(int32_t n_nodes, int32_t n_branches, int64_t batch, 
   int rc = check_shape(n_nodes, n_branches);
   if (rc) return rc;
   if (!bytes) return pbn::set_error(PBN_EINVAL, "null bytes");
-  if (batch < kRows || batch % kRows || batch > (1 << 20))
-    return pbn::set_error(PBN_EINVAL, "fused BDQ update: batch a multiple of 16, 16..2^20");
+  if ((rc = check_batch(batch))) return rc;
   if (learn_bwd_lds(n_branches + 1, 16 * ((n_nodes + 16) / 16), n_branches) > 160 * 1024)
     return pbn::set_error(PBN_EINVAL, "fused BDQ update: (n_branches + 1) x (n_nodes + 1) too large for one block's LDS");
   *bytes = make_work(n_nodes, n_branches + 1, batch).total * (int64_t)sizeof(float);
@@ -1232,15 +1269,32 @@ int pbn_bdq_pack(const pbn_net* net, int32_t n_branches, const float* d_params, 
   return PBN_OK;
 }
 
-int pbn_bdq_learn(const pbn_net* net, int64_t batch, const int64_t* d_idx, int64_t capacity, const uint32_t* d_state,
-                  const uint32_t* d_next_state, const uint8_t* d_target, const int32_t* d_action, int32_t n_branches,
-                  const float* d_reward, const uint8_t* d_done, float* d_params, float* d_Tq,
-                  const float* d_target_params, const float* d_target_Tq, float* d_adam_m, float* d_adam_v,
-                  float* d_adam_step, float lr, float beta1, float beta2, float eps, float gamma, float grad_clamp,
-                  float slope, void* d_workspace, int64_t workspace_bytes, float* d_loss, float* d_grad,
-                  const pbn_frame_advance* advance, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// pbn_bdq_learn and pbn_bdq_learn_per: the argument checks, the LearnArgs fill and the three
+// launches.  per: the rows carry importance weights (learn_bwd_kernel<true>); its own arguments and
+// the shape arguments that need no net are checked first, before the net is looked at.
+int learn_launch(bool per, const pbn_net* net, int64_t batch, const int64_t* d_idx, int64_t capacity,
+                 const uint32_t* d_state, const uint32_t* d_next_state, const uint8_t* d_target,
+                 const int32_t* d_action, int32_t n_branches, const float* d_reward, const uint8_t* d_done,
+                 float* d_params, float* d_Tq, const float* d_target_params, const float* d_target_Tq, float* d_adam_m,
+                 float* d_adam_v, float* d_adam_step, float lr, float beta1, float beta2, float eps, float gamma,
+                 float grad_clamp, float slope, void* d_workspace, int64_t workspace_bytes, float* d_loss,
+                 float* d_grad, const float* d_weights, float replay_constant, float* d_priority,
+                 const pbn_frame_advance* advance, void* stream) {
+  int rc;
+  if (per) {
+    if (!d_weights) return pbn::set_error(PBN_EINVAL, "pbn_bdq_learn_per: null d_weights");
+    if (!d_priority) return pbn::set_error(PBN_EINVAL, "pbn_bdq_learn_per: null d_priority");
+    if ((uintptr_t)d_weights & 3u) return pbn::set_error(PBN_EINVAL, "pbn_bdq_learn_per: d_weights must be 4-byte aligned");
+    if ((uintptr_t)d_priority & 3u) return pbn::set_error(PBN_EINVAL, "pbn_bdq_learn_per: d_priority must be 4-byte aligned");
+    if ((rc = check_branches(n_branches))) return rc;
+    if ((rc = check_batch(batch))) return rc;
+  }
   pbn::NetView nv;
-  int rc = pbn::net_view(net, &nv);
+  rc = pbn::net_view(net, &nv);
   if (rc) return rc;
   if ((rc = pbn::check_device(net))) return rc;
   const int N = nv.n_nodes;
@@ -1315,6 +1369,9 @@ int pbn_bdq_learn(const pbn_net* net, int64_t batch, const int64_t* d_idx, int64
   a.partial = ws + w.partial;
   a.loss = d_loss;
   a.grad = d_grad;
+  a.wts = per ? d_weights : nullptr;
+  a.prio = per ? d_priority : nullptr;
+  a.rconst = per ? replay_constant : 0.f;
   a.stamps = nullptr;
 #ifdef PBN_STAMPS
   a.stamps = g_lstamps;
@@ -1341,10 +1398,11 @@ int pbn_bdq_learn(const pbn_net* net, int64_t batch, const int64_t* d_idx, int64
   hipLaunchKernelGGL(learn_fwd_kernel, dim3(3 * tiles), dim3(kThreads), lds_f, s, a);
   if (hipGetLastError() != hipSuccess) return pbn::set_error(PBN_EDEVICE, "learn_fwd_kernel launch failed");
   const size_t lds_b = learn_bwd_lds(H, a.Apad, n_branches);
-  if (lds_b > 64 * 1024 && hipFuncSetAttribute((const void*)learn_bwd_kernel,
+  void (*const bwd)(LearnArgs) = per ? learn_bwd_kernel<true> : learn_bwd_kernel<false>;
+  if (lds_b > 64 * 1024 && hipFuncSetAttribute((const void*)bwd,
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b) != hipSuccess)
     return pbn::set_error(PBN_EDEVICE, "hipFuncSetAttribute failed");
-  hipLaunchKernelGGL(learn_bwd_kernel, dim3(tiles), dim3(kThreads), lds_b, s, a);
+  hipLaunchKernelGGL(bwd, dim3(tiles), dim3(kThreads), lds_b, s, a);
   if (hipGetLastError() != hipSuccess) return pbn::set_error(PBN_EDEVICE, "learn_bwd_kernel launch failed");
   const int ntasks = 16 * N + (kD1 / 16) * (kD0 / 16) + (kD2 / 16) * (kD1 / 16) + (kD3 / 16) * (kD2 / 16) +
                      (H * kDH / 16) * (kD3 / 16) + H * (a.Apad / 16) * (kDH / 16);
@@ -1361,6 +1419,37 @@ int pbn_bdq_learn(const pbn_net* net, int64_t batch, const int64_t* d_idx, int64
   }
   if (hipGetLastError() != hipSuccess) return pbn::set_error(PBN_EDEVICE, "learn_apply_kernel launch failed");
   return PBN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pbn_bdq_learn(const pbn_net* net, int64_t batch, const int64_t* d_idx, int64_t capacity, const uint32_t* d_state,
+                  const uint32_t* d_next_state, const uint8_t* d_target, const int32_t* d_action, int32_t n_branches,
+                  const float* d_reward, const uint8_t* d_done, float* d_params, float* d_Tq,
+                  const float* d_target_params, const float* d_target_Tq, float* d_adam_m, float* d_adam_v,
+                  float* d_adam_step, float lr, float beta1, float beta2, float eps, float gamma, float grad_clamp,
+                  float slope, void* d_workspace, int64_t workspace_bytes, float* d_loss, float* d_grad,
+                  const pbn_frame_advance* advance, void* stream) {
+  return learn_launch(false, net, batch, d_idx, capacity, d_state, d_next_state, d_target, d_action, n_branches,
+                      d_reward, d_done, d_params, d_Tq, d_target_params, d_target_Tq, d_adam_m, d_adam_v, d_adam_step,
+                      lr, beta1, beta2, eps, gamma, grad_clamp, slope, d_workspace, workspace_bytes, d_loss, d_grad,
+                      nullptr, 0.f, nullptr, advance, stream);
+}
+
+int pbn_bdq_learn_per(const pbn_net* net, int64_t batch, const int64_t* d_idx, int64_t capacity,
+                      const uint32_t* d_state, const uint32_t* d_next_state, const uint8_t* d_target,
+                      const int32_t* d_action, int32_t n_branches, const float* d_reward, const uint8_t* d_done,
+                      float* d_params, float* d_Tq, const float* d_target_params, const float* d_target_Tq,
+                      float* d_adam_m, float* d_adam_v, float* d_adam_step, float lr, float beta1, float beta2,
+                      float eps, float gamma, float grad_clamp, float slope, void* d_workspace, int64_t workspace_bytes,
+                      float* d_loss, float* d_grad, const float* d_weights, float replay_constant, float* d_priority,
+                      const pbn_frame_advance* advance, void* stream) {
+  return learn_launch(true, net, batch, d_idx, capacity, d_state, d_next_state, d_target, d_action, n_branches,
+                      d_reward, d_done, d_params, d_Tq, d_target_params, d_target_Tq, d_adam_m, d_adam_v, d_adam_step,
+                      lr, beta1, beta2, eps, gamma, grad_clamp, slope, d_workspace, workspace_bytes, d_loss, d_grad,
+                      d_weights, replay_constant, d_priority, advance, stream);
 }
 
 }  // extern "C"

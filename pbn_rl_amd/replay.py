@@ -581,27 +581,53 @@ class FusedBDQUpdate:
         """BatchedBDQ's weight-derived operands as views of the flat buffer (no assembly kernels)."""
         return self._acting
 
-    def update(self, replay: "DeviceReplay", idx: torch.Tensor, advance=None) -> torch.Tensor:
+    @staticmethod
+    def check_per_args(B: int, device, weights, priorities_out) -> None:
+        """update()'s importance-weight arguments: both or neither, contiguous float32 [B] tensors
+        on ``device``.  Raises ValueError naming the offending argument."""
+        if weights is None:
+            if priorities_out is not None:
+                raise ValueError("priorities_out needs weights")
+            return
+        if priorities_out is None:
+            raise ValueError("priorities_out is required with weights")
+        for name, t in (("weights", weights), ("priorities_out", priorities_out)):
+            if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.shape != (B,)
+                    or not t.is_contiguous() or t.device != torch.device(device)):
+                raise ValueError(f"{name} must be a contiguous float32 [{B}] tensor on {device}")
+
+    def update(self, replay: "DeviceReplay", idx: torch.Tensor, advance=None, weights: Optional[torch.Tensor] = None,
+               priorities_out: Optional[torch.Tensor] = None, replay_constant: float = 1e-5) -> torch.Tensor:
         """One update on ring rows ``idx`` (int64, ``batch_size`` of them); returns the loss buffer
         (overwritten by the next update).  ``advance``: an ``_lib.FrameAdvance`` whose counters
         the update's last launch advances (and the next frame's rows it draws; BDQLearner's
-        captured frame)."""
+        captured frame).
+
+        ``weights`` (float32 [B] on the device; prioritised replay's importance weights, by batch
+        position): the weighted update of bdq_update, loss = mean_b w_b l_b, as the same three
+        launches (``pbn_bdq_learn_per``); ``priorities_out`` (float32 [B], required with weights)
+        receives |w_b l_b| + ``replay_constant`` from the backward's TD pass."""
         if idx.shape != (self.B,) or idx.dtype != torch.int64:
             raise ValueError(f"idx must be {self.B} int64 ring indices")
+        self.check_per_args(self.B, self.q_flat.device, weights, priorities_out)
         self.sync()
         L = _lib.load()
         b1, b2 = self.betas
+        args = (self.net.handle, self.B, idx.contiguous().data_ptr(), replay.capacity,
+                replay.state.data_ptr(), replay.next_state.data_ptr(), replay.target.data_ptr(),
+                replay.action.data_ptr(), self.K, replay.reward.data_ptr(),
+                replay.done.data_ptr(), self.q_flat.data_ptr(), self.q_image.data_ptr(),
+                self.t_flat.data_ptr(), self.t_image.data_ptr(), self.m.data_ptr(),
+                self.v.data_ptr(), self.step.data_ptr(), self.lr, b1, b2, self.eps, self.gamma,
+                self.grad_clamp, self.slope, self.work.data_ptr(), self.work.numel() * 4,
+                self.loss.data_ptr(), self.grad.data_ptr() if self.grad is not None else None)
+        adv = ctypes.byref(advance) if advance is not None else None
         with torch.cuda.device(self.q_flat.device):
-            _lib.check(L.pbn_bdq_learn(self.net.handle, self.B, idx.contiguous().data_ptr(), replay.capacity,
-                                       replay.state.data_ptr(), replay.next_state.data_ptr(), replay.target.data_ptr(),
-                                       replay.action.data_ptr(), self.K, replay.reward.data_ptr(),
-                                       replay.done.data_ptr(), self.q_flat.data_ptr(), self.q_image.data_ptr(),
-                                       self.t_flat.data_ptr(), self.t_image.data_ptr(), self.m.data_ptr(),
-                                       self.v.data_ptr(), self.step.data_ptr(), self.lr, b1, b2, self.eps, self.gamma,
-                                       self.grad_clamp, self.slope, self.work.data_ptr(), self.work.numel() * 4,
-                                       self.loss.data_ptr(), self.grad.data_ptr() if self.grad is not None else None,
-                                       ctypes.byref(advance) if advance is not None else None,
-                                       self._stream()), "pbn_bdq_learn")
+            if weights is None:
+                _lib.check(L.pbn_bdq_learn(*args, adv, self._stream()), "pbn_bdq_learn")
+            else:
+                _lib.check(L.pbn_bdq_learn_per(*args, weights.data_ptr(), float(replay_constant),
+                                               priorities_out.data_ptr(), adv, self._stream()), "pbn_bdq_learn_per")
         if not torch.cuda.is_current_stream_capturing():
             self.mark_updated()   # (a captured update is marked by each replay: BDQLearner._replay_frame)
         return self.loss[0]
@@ -628,11 +654,15 @@ class BDQLearner:
     update (bdq_update + torch.optim.Adam).
 
     ``prioritised=True`` (GPU only) trains from a PrioritisedDeviceReplay as DDQNPER does
-    (ddqn_per/__init__.py:468-483): every update is sample -> gather -> importance-weighted
-    bdq_update -> update_priorities with |w_b l_b| + ``replay_constant``.  It uses the PyTorch
-    update (``fused=True`` with it raises: the fused update takes no weights).  ``per_beta`` moves
-    to ``per_max_beta`` in ``per_beta_steps`` equal steps, one per update; ``capture()`` works
-    with it, the host mirroring beta as it mirrors epsilon."""
+    (ddqn_per/__init__.py:468-483): every update is sample -> importance-weighted update ->
+    update_priorities with |w_b l_b| + ``replay_constant``.  By default (``fused=None``) the
+    update is the PyTorch one (gather -> bdq_update); ``fused=True`` runs it as FusedBDQUpdate's
+    three launches, the weights going into and the priorities coming out of the backward's TD
+    pass (``pbn_bdq_learn_per``).  Either way every update samples for itself (a prioritised
+    sample depends on the priorities the update before it wrote), so the fused prioritised
+    learner does not pre-draw its rows as the fused uniform one does.  ``per_beta`` moves to
+    ``per_max_beta`` in ``per_beta_steps`` equal steps, one per update; ``capture()`` works with
+    it, the host mirroring beta as it mirrors epsilon."""
 
     def __init__(self, env: VectorPBNEnv, qnet: Optional[BranchingQNetwork] = None, *, capacity: int = 10 ** 4,
                  batch_size: int = 256, learning_rate: float = 1e-4, gamma: float = 0.999,
@@ -641,12 +671,12 @@ class BDQLearner:
                  graphable: bool = False, blas: Optional[str] = "cublas", fused: Optional[bool] = None,
                  prioritised: bool = False, per_alpha: float = 0.6, per_beta: float = 0.4, per_max_beta: float = 1.0,
                  per_beta_steps: int = 10_000, replay_constant: float = 1e-5):
-        if prioritised:   # (contradictory arguments: refused before the env is looked at)
-            if fused:
-                raise ValueError("prioritised replay uses the PyTorch update: fused=True takes no importance weights")
+        if prioritised:   # (arguments that cannot work: refused before the env is looked at)
             if batch_size > 1024:
                 raise ValueError("prioritised replay samples at most 1024 rows per update")
-            fused = False
+            fused = bool(fused)   # (the default stays the PyTorch update)
+        if fused and (not isinstance(env, VectorPBNEnv) or env.device.type != "cuda"):
+            raise ValueError("fused update: needs a VectorPBNEnv on the GPU")
         if not env.keep_final_state:
             raise ValueError("BDQLearner needs the env's final_state (keep_final_state=True)")
         self.prioritised = bool(prioritised)
@@ -695,9 +725,11 @@ class BDQLearner:
         self.gen = torch.Generator(device=env.device)
         self.gen.manual_seed(seed)
         self.seed = int(seed)
-        if self.fused is not None:
+        if self.fused is not None and not self.prioritised:
             # the fused learner draws its rows from the REPLAY Philox stream (pbn_replay_advance):
-            # all updates_per_frame batches of a frame in one draw, eager or captured
+            # all updates_per_frame batches of a frame in one draw, eager or captured.  (Not the
+            # prioritised one: a prioritised sample depends on the priorities the update before
+            # it wrote, so every update samples for itself)
             self._draw_t = torch.zeros(1, dtype=torch.int64, device=env.device)
             self._idx = torch.empty(updates_per_frame * batch_size, dtype=torch.int64, device=env.device)
         self.last_loss: Optional[torch.Tensor] = None
@@ -742,11 +774,13 @@ class BDQLearner:
         self.frames += 1
         if self.replay.size >= self.learning_starts:
             self.epsilon = max(self.epsilon_final, self.epsilon - self.epsilon_step)
-            if self.fused is not None:
+            if self.fused is not None and not self.prioritised:
                 size_t = torch.full((1,), self.replay.size, dtype=torch.int64, device=env.device)
                 self.replay.sample_rows(self._idx, self.seed, self._draw_t, size_t)
             for u in range(self.updates_per_frame):
-                if self.fused is not None:
+                if self.prioritised:
+                    self.last_loss = self._update_prioritised()
+                elif self.fused is not None:
                     self.last_loss = self.fused.update(self.replay, self._idx[u * self.batch_size:(u + 1) * self.batch_size])
                 elif self.prioritised:
                     self.last_loss = self._update_prioritised()
@@ -777,6 +811,11 @@ class BDQLearner:
         """sample -> gather -> weighted update -> update_priorities (DDQNPER._learn_step)."""
         rp = self.replay
         idx, w = rp.sample(self.batch_size, size_t)
+        if self.fused is not None:   # the weights into, and the priorities out of, the fused update's TD pass
+            loss = self.fused.update(rp, idx, weights=w, priorities_out=self._prio,
+                                     replay_constant=self.replay_constant)
+            rp.update_priorities(idx, self._prio, size_t)
+            return loss
         batch = rp.gather(idx, self.env.net)
         loss = bdq_update(self.q, self.target, self.opt, batch, self.gamma, target_weights=self._target_weights(),
                           weights=w, priorities_out=self._prio, replay_constant=self.replay_constant)
@@ -830,7 +869,7 @@ class BDQLearner:
                 rp.action.data_ptr(), rp.reward.data_ptr(), rp.done.data_ptr(), self.agent.actions.data_ptr(),
                 rp.action.shape[1], _lib.FLAG_TERMINATED | _lib.FLAG_TRUNCATED, self._done_buf.data_ptr())
         self._adv = None
-        if self.fused is not None:
+        if self.fused is not None and not self.prioritised:
             # the fused update's last launch advances the frame's counters and draws the next
             # frame's rows (pbn_frame_advance): the first replayed frame's rows are drawn now, over
             # the fill level its store will leave (what pbn_replay_advance drew inside the frame)
@@ -870,8 +909,10 @@ class BDQLearner:
                                  advance=False, state_copy=(env.state, env._state_next),
                                  target_copy=(self._tgt_prev, env.target))
         # then the counters: the step index, the ring position and fill level, epsilon (and, fused,
-        # the next frame's rows) advance in the update's last launch or in pbn_replay_advance
-        fused = self.fused is not None
+        # the next frame's rows) advance in the update's last launch or in pbn_replay_advance.  A
+        # prioritised frame, fused or not, advances them before its updates: its sample must see the
+        # fill level after the frame's store, as the eager path does
+        fused = self.fused is not None and not self.prioritised
         L = _lib.load()
         if not fused:   # (fused: the update's last launch advances them, pbn_frame_advance)
             with torch.cuda.device(env.device):
