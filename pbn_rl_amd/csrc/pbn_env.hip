@@ -24,12 +24,13 @@
 #include <stdlib.h>
 
 #include <algorithm>
-#include <type_traits>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/pbn_env.h"
 #include "bitslice.h"
+#include "net_image.h"
 #include "net_view.h"
 #include "philox.h"
 
@@ -59,51 +60,36 @@ int fail(int code, const std::string& msg) {
     if (e_ != hipSuccess) return fail(PBN_EDEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
   } while (0)
 
-using StepFn = void (*)(StepArgs);
-
-
-template <int W, int V>
-StepFn pick_wave_w(int B) {
-  switch (B) {
-    case 4: return pbn_step_wave<W, 4, V>;
-    case 8: return pbn_step_wave<W, 8, V>;
-    case 12: return pbn_step_wave<W, 12, V>;
-    case 16: return pbn_step_wave<W, 16, V>;
+// a device allocation, freed with its owner
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { (void)hipFree(p_); }
+  // allocates count elements (at least one byte) and fills them from src, if given
+  template <typename T>
+  int upload(const T* src, size_t count) {
+    const size_t bytes = count * sizeof(T);
+    HIP_OK(hipMalloc(&p_, std::max<size_t>(bytes, 1)));
+    if (src && bytes) HIP_OK(hipMemcpy(p_, src, bytes, hipMemcpyHostToDevice));
+    return PBN_OK;
   }
-  return nullptr;
-}
+  template <typename T>
+  T* as() const { return static_cast<T*>(p_); }
 
-template <int V>
-StepFn pick_wave(int W, int B) {
-  switch (W) {
-    case 1: return pick_wave_w<1, V>(B);
-    case 2: return pick_wave_w<2, V>(B);
-    case 3: return pick_wave_w<3, V>(B);
-    case 4: return pick_wave_w<4, V>(B);
-  }
-  return nullptr;
-}
-
-template <int W, bool MANY>
-StepFn pick_pipe_w(int B) {
-  switch (B) {
-    case 4: return pbn_rollout_pipe<W, 4, MANY>;
-    case 8: return pbn_rollout_pipe<W, 8, MANY>;
-    case 12: return pbn_rollout_pipe<W, 12, MANY>;
-    case 16: return pbn_rollout_pipe<W, 16, MANY>;
-  }
-  return nullptr;
-}
+ private:
+  void* p_ = nullptr;
+};
 
 // many: some node has more than kNodeRecs functions (the instance that carries those chains)
 StepFn pick_pipe(int W, int B, bool many) {
-  switch (W) {
-    case 1: return many ? pick_pipe_w<1, true>(B) : pick_pipe_w<1, false>(B);
-    case 2: return many ? pick_pipe_w<2, true>(B) : pick_pipe_w<2, false>(B);
-    case 3: return many ? pick_pipe_w<3, true>(B) : pick_pipe_w<3, false>(B);
-    case 4: return many ? pick_pipe_w<4, true>(B) : pick_pipe_w<4, false>(B);
-  }
-  return nullptr;
+  return for_state_words(W, [&](auto w) {
+    constexpr int kW = decltype(w)::value;
+    return many ? for_prob_bits(B, [](auto b) -> StepFn { return pbn_rollout_pipe<kW, decltype(b)::value, true>; })
+                : for_prob_bits(B, [](auto b) -> StepFn { return pbn_rollout_pipe<kW, decltype(b)::value, false>; });
+  });
 }
 
 using ResetFn = void (*)(const int32_t*, const uint32_t*, int, int, int, uint64_t, uint64_t, uint64_t, int64_t,
@@ -121,48 +107,15 @@ ResetFn pick_reset(int W) {
 }  // namespace
 
 struct pbn_net {
+  StepArgs base{};   // the launch arguments fixed at create (fill_args adds the key and the env range)
+  DevBuf tab, att_start, att_states, att_first, fcompact, nrec, sthr, sthr_pk;
+  StepFn kernels[kNumKernels] = {};   // nullptr: no instance for this net
+  ResetFn reset = nullptr;
+  RouteNet route{};
   int device = 0;
   int n_cus = 256;   // compute units of the device (the pipelined rollout's priority choice)
-  int n_nodes = 0, W = 0, B = 0, horizon = 0, n_attr = 0, n_states = 0;
-  int cdf_len = 0, hash_bits = 0, hash_probes = 0, tab_words = 0;
-  uint32_t hash_mult[4] = {0, 0, 0, 0};
-  int wave_words = 0;
-  int att_off = 0;
-  int sel_off = 0;
-  int nrec_off = 0;
-  int cm_off = 0;   // the pipelined kernel's threshold digit masks in the image (W == 1)
-  int n_cls = 0;
-  uint32_t uthr[kNodeRecs] = {0, 0, 0, 0};
-  int gap_exact = 1;
-  int gap_lut_off = 0, gap_shift = 0, gap_nb = 0;
-  float inv_log2q = 0.f;
-  uint4* d_fcompact = nullptr;
-  uint4* d_nrec = nullptr;
-  uint32_t* d_sthr = nullptr;   // settle law: thresholds scaled to 16 bits [lq][32W] (StepArgs::sthr)
-  uint32_t* d_sthr_pk = nullptr;   // the same, packed biased node pairs [lq][W][16] (StepArgs::sthr_pk)
-  int settle_pk = 0;
-  int n_funcs = 0;
-  size_t lds_wave = 0;
-  StepFn wave1 = nullptr;       // single step (pbn_step)
-  StepFn wave_lean = nullptr;   // rollout, one wave per group (networks with gates)
-  StepFn wave_settle = nullptr;       // pbn_step under the settle law (settle_max >= 2)
-  StepFn wave_settle_lean = nullptr;  // pbn_rollout under the settle law (networks with gates)
-  StepFn pipe_settle = nullptr;       // pbn_rollout under the settle law, three waves per group pair
-  size_t lds_settle = 0;
-  int settle_max = 0;
-  StepFn pipe = nullptr;        // rollout, three waves per group pair (every other network)
-  size_t lds_pipe = 0;
-  int n_gates = 0, n_glayers = 0, gate_off = 0, glayer_off = 0;   // lowered wide functions
-  int max_nf = 0, lq = 1, slot_words = 0, slot_words_settle = 0;
-  uint32_t n1_magic = 0, am1_magic = 0;   // ceil(2^32 / (N + 1)), ceil(2^32 / (A - 1))
-  uint64_t x_mult = 0;
-  int att_single = 0;                     // every attractor is a single state
-  int force_roll = 0;        // PBN_ROLL env override: 2 = lean (wave kernel), 3 = pipe
-  ResetFn reset = nullptr;
-  uint32_t* d_tab = nullptr;
-  int32_t* d_att_start = nullptr;
-  uint32_t* d_att_states = nullptr;
-  uint32_t* d_att_first = nullptr;        // [n_attr][W]: each attractor's first state
+  int W = 0;
+  int slot_words_settle = 0;   // StepArgs::slot_words of pbn_rollout_settle
 };
 
 namespace pbn {
@@ -172,13 +125,13 @@ int set_error(int code, const char* msg) { return fail(code, msg); }
 int net_view(const pbn_net* net, NetView* v) {
   if (!net || !v) return fail(PBN_EINVAL, "null net");
   v->device = net->device;
-  v->n_nodes = net->n_nodes;
+  v->n_nodes = net->base.n_nodes;
   v->W = net->W;
-  v->n_attr = net->n_attr;
-  v->n_states = net->n_states;
-  v->att_start = net->d_att_start;
-  v->att_states = net->d_att_states;
-  v->att_first = net->d_att_first;
+  v->n_attr = net->base.n_attr;
+  v->n_states = net->base.n_states;
+  v->att_start = net->base.att_start;
+  v->att_states = net->base.att_states;
+  v->att_first = net->att_first.as<uint32_t>();
   return PBN_OK;
 }
 
@@ -194,88 +147,107 @@ int check_device(const pbn_net* net) {
 
 namespace {
 
-void free_net(pbn_net* net) {
-  if (!net) return;
-  (void)hipFree(net->d_fcompact);
-  (void)hipFree(net->d_nrec);
-  (void)hipFree(net->d_sthr);
-  (void)hipFree(net->d_sthr_pk);
-  (void)hipFree(net->d_tab);
-  (void)hipFree(net->d_att_start);
-  (void)hipFree(net->d_att_states);
-  (void)hipFree(net->d_att_first);
-  delete net;
+int upload_image(const pbn::NetImage& im, const pbn_net_desc* d, pbn_net* net) {
+  const int A = im.n_attr, S = im.n_states;
+  int rc;
+  if ((rc = net->fcompact.upload(im.fcompact.data(), im.fcompact.size())) ||
+      (rc = net->nrec.upload(im.nrec.data(), im.nrec.size())) ||
+      (rc = net->sthr.upload(im.sthr.data(), im.sthr.size())) ||
+      (rc = net->sthr_pk.upload(im.sthr_pk.data(), im.sthr_pk.size())) ||
+      (rc = net->tab.upload(im.tab.data(), im.tab.size())) ||
+      (rc = net->att_start.upload(A ? d->attractor_start : nullptr, (size_t)A + 1)) ||
+      (rc = net->att_states.upload(S ? d->attractor_states : nullptr, (size_t)S * im.W)) ||
+      (rc = net->att_first.upload(A ? im.att_first.data() : nullptr, im.att_first.size())))
+    return rc;
+  return PBN_OK;
 }
 
-template <typename T>
-int upload(T** dst, const T* src, size_t count) {
-  if (count == 0) count = 1;
-  HIP_OK(hipMalloc(reinterpret_cast<void**>(dst), count * sizeof(T)));
-  if (src) HIP_OK(hipMemcpy(*dst, src, count * sizeof(T), hipMemcpyHostToDevice));
-  return 0;
+void set_base(const pbn::NetImage& im, pbn_net* net) {
+  StepArgs& a = net->base;
+  a.tab = net->tab.as<uint32_t>();
+  a.att_start = net->att_start.as<int32_t>();
+  a.att_states = net->att_states.as<uint32_t>();
+  a.fcompact = net->fcompact.as<uint4>();
+  a.nrec = net->nrec.as<uint4>();
+  a.sthr = net->sthr.as<uint32_t>();
+  a.sthr_pk = net->sthr_pk.as<uint32_t>();
+  a.n_steps = 1;
+  a.n_nodes = im.n_nodes;
+  a.n_attr = im.n_attr;
+  a.horizon = im.horizon;
+  a.cdf_len = im.cdf_len;
+  a.hash_bits = im.n_attr ? im.hash_bits : 0;
+  a.hash_probes = im.hash_probes;
+  memcpy(a.hash_mult, im.hash_mult, sizeof a.hash_mult);
+  a.tab_words = im.tab_words;
+  a.prob_bits = im.prob_bits;
+  a.n_funcs = im.n_funcs;
+  a.wave_words = im.wave_words;
+  a.gap_exact = im.gap_exact;
+  a.gap_lut_off = im.gap_lut_off;
+  a.gap_shift = im.gap_shift;
+  a.gap_nb = im.gap_nb;
+  a.inv_log2q = im.inv_log2q;
+  a.n_states = im.n_states;
+  a.att_off = im.att_off;
+  a.sel_off = im.sel_off;
+  a.nrec_off = im.nrec_off;
+  a.cm_off = im.cm_off;
+  a.n_cls = im.n_cls;
+  memcpy(a.uthr, im.uthr, sizeof a.uthr);
+  a.max_nf = im.max_nf;
+  a.lq = im.lq;
+  a.slot_words = im.slot_words;
+  a.gate_off = im.gate_off;
+  a.glayer_off = im.glayer_off;
+  a.n_glayers = im.n_glayers;
+  a.att_single = im.att_single;
+  a.n1_magic = im.n1_magic;
+  a.am1_magic = im.am1_magic;
+  a.x_mult = im.x_mult;
+  a.settle_max = im.settle_max;
+  a.settle_pk = im.settle_pk;
 }
 
-// open-addressing hash of the attractor states; deterministic multiplier search
-bool build_hash(const std::vector<std::vector<uint32_t>>& states, const std::vector<uint32_t>& ids, int W,
-                int* bits_out, int* probes_out, uint32_t mult_out[4], std::vector<uint32_t>* image) {
-  const size_t S = states.size();
-  int bits = 1;
-  while ((size_t(1) << bits) < 2 * S) ++bits;
-  uint64_t rng = 0x9E3779B97F4A7C15ull;
-  auto next = [&rng]() {
-    rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17;
-    return (uint32_t)(rng >> 11) | 1u;
-  };
-  // prefer a collision-free table (one probe per lookup) up to 16x the minimal size
-  const int min_bits = bits;
-  for (; bits <= kMaxHashBits; ++bits) {
-    const uint32_t size = 1u << bits, mask = size - 1;
-    int best_probes = 1 << 30;
-    uint32_t best_mult[4] = {0, 0, 0, 0};
-    for (int trial = 0; trial < 64; ++trial) {
-      uint32_t mult[4];
-      for (int w = 0; w < 4; ++w) mult[w] = next();
-      std::vector<int> slot_used(size, 0);
-      int probes = 1;
-      for (size_t k = 0; k < S; ++k) {
-        uint32_t h = 0;
-        for (int w = 0; w < W; ++w) h += states[k][w] * mult[w];
-        h >>= (32 - bits);
-        int p = 0;
-        while (slot_used[(h + p) & mask]) ++p;
-        slot_used[(h + p) & mask] = 1;
-        probes = std::max(probes, p + 1);
-      }
-      if (probes < best_probes) {
-        best_probes = probes;
-        std::copy(mult, mult + 4, best_mult);
-      }
-      if (best_probes == 1) break;
-    }
-    const bool accept = best_probes == 1 || (best_probes <= 4 && bits >= std::min(min_bits + 4, kMaxHashBits));
-    if (accept || bits == kMaxHashBits) {
-      const int HS = W == 1 ? 2 : (W <= 3 ? 4 : 8);   // HashStride<W>
-      image->assign((size_t)HS * size, 0u);
-      std::vector<int> used(size, 0);
-      for (uint32_t s = 0; s < size; ++s) (*image)[(size_t)s * HS + W] = 0xFFFFFFFFu;
-      for (size_t k = 0; k < S; ++k) {
-        uint32_t h = 0;
-        for (int w = 0; w < W; ++w) h += states[k][w] * best_mult[w];
-        h >>= (32 - bits);
-        int p = 0;
-        while (used[(h + p) & mask]) ++p;
-        const uint32_t slot = (h + p) & mask;
-        used[slot] = 1;
-        for (int w = 0; w < W; ++w) (*image)[(size_t)slot * HS + w] = states[k][w];
-        (*image)[(size_t)slot * HS + W] = ids[k];
-      }
-      *bits_out = bits;
-      *probes_out = best_probes;
-      std::copy(best_mult, best_mult + 4, mult_out);
-      return true;
-    }
+// the kernel instances of the net's (W, B), and what route_launch chooses among them by
+void pick_kernels(const pbn::NetImage& im, pbn_net* net) {
+  const int W = im.W, B = im.prob_bits;
+  const bool many = im.max_nf > kNodeRecs;
+  net->kernels[kWave1] = step_kernel_for(W, B, [](auto w, auto b) -> StepFn {
+    return pbn_step_wave<decltype(w)::value, decltype(b)::value, 1>;
+  });
+  net->kernels[kWaveLean] = step_kernel_for(W, B, [](auto w, auto b) -> StepFn {
+    return pbn_step_wave<decltype(w)::value, decltype(b)::value, 2>;
+  });
+  net->kernels[kWaveSettle] = reinterpret_cast<StepFn>(pbn::settle_kernel(W, B, 0));
+  net->kernels[kWaveSettleLean] = reinterpret_cast<StepFn>(pbn::settle_kernel(W, B, 1));
+  net->kernels[kPipe] = pick_pipe(W, B, many);
+  if (!many) net->kernels[kPipeSettle] = reinterpret_cast<StepFn>(pbn::settle_pipe_kernel(W, B));
+  net->reset = pick_reset(W);
+  net->W = W;
+  net->slot_words_settle = im.slot_words_settle;
+  net->route.settle = im.settle_max >= 2;
+  net->route.n_gates = im.n_gates;
+  net->route.has_pipe_settle = net->kernels[kPipeSettle] != nullptr;
+  net->route.lds_wave = im.lds_wave;
+  net->route.lds_pipe = im.lds_pipe;
+  net->route.lds_settle = im.lds_settle;
+  if (const char* env = getenv("PBN_ROLL")) {
+    if (!strcmp(env, "lean")) net->route.force_roll = 2;
+    if (!strcmp(env, "pipe")) net->route.force_roll = 3;
   }
-  return false;
+}
+
+// lets every kernel the net can run ask for its LDS
+int raise_lds_limits(const pbn_net& net) {
+  for (int k = 0; k < kNumKernels; ++k) {
+    const size_t bytes = kernel_lds_bytes(net.route, (Kernel)k);
+    if (!net.kernels[k] || bytes > kLdsDeviceBytes) continue;   // unusable for this net; never picked
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(net.kernels[k]),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
+      return fail(PBN_EDEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+  }
+  return PBN_OK;
 }
 
 }  // namespace
@@ -376,411 +348,21 @@ int pbn_net_words(const pbn_net* net) { return net ? net->W : PBN_EINVAL; }
 int pbn_net_create(const pbn_net_desc* d, pbn_net** out) {
   if (!d || !out) return fail(PBN_EINVAL, "null descriptor/out");
   *out = nullptr;
-  const int N = d->n_nodes;
-  if (N < 1 || N > PBN_MAX_NODES) return fail(PBN_EINVAL, "n_nodes out of range 1..128");
-  if (!(d->prob_bits == 4 || d->prob_bits == 8 || d->prob_bits == 12 || d->prob_bits == 16))
-    return fail(PBN_EINVAL, "prob_bits must be 4, 8, 12 or 16");
-  if (d->horizon < 0 || d->horizon > 255) return fail(PBN_EINVAL, "horizon out of range 0..255");
-  if (d->settle_max < 0 || d->settle_max > PBN_MAX_SETTLE) return fail(PBN_EINVAL, "settle_max out of range 0..4096");
-  if (d->n_attractors < 0 || d->n_attractors > PBN_MAX_ATTRACTORS)
-    return fail(PBN_EINVAL, "n_attractors out of range 0..254");
-  if (!d->node_func_start || !d->func_arity || !d->func_inputs || !d->func_table || !d->func_threshold ||
-      !d->perturb_cdf || !d->reward_table)
-    return fail(PBN_EINVAL, "null table in descriptor");
-  const int W = (N + 31) / 32;
-  const uint32_t one = 1u << d->prob_bits;
-  const int n_gates = d->n_gates;
-  if (n_gates < 0 || n_gates > PBN_MAX_GATES || 32 * W + n_gates > 256)
-    return fail(PBN_EINVAL, "n_gates out of range (32 * W + n_gates must be <= 256)");
-  if (n_gates && (!d->gate_arity || !d->gate_inputs || !d->gate_table)) return fail(PBN_EINVAL, "null gate table");
-  // gate levels: 1 + the deepest gate input (nodes are level 0)
-  std::vector<int> glevel(n_gates, 1);
-  for (int g = 0; g < n_gates; ++g) {
-    const int k = d->gate_arity[g];
-    if (k < 0 || k > PBN_MAX_ARITY) return fail(PBN_EINVAL, "gate arity must be 0..4");
-    if (k < 5 && (1u << k) < 32 && (d->gate_table[g] >> (1u << k)) != 0u)
-      return fail(PBN_EINVAL, "gate truth table has bits beyond 2^arity");
-    for (int j = 0; j < k; ++j) {
-      const int r = d->gate_inputs[4 * g + j];
-      if (r < 0 || r >= N + g) return fail(PBN_EINVAL, "gate input must be a node or an earlier gate");
-      if (r >= N) glevel[g] = std::max(glevel[g], glevel[r - N] + 1);
-    }
-  }
-  if (d->node_func_start[0] != 0 || d->node_func_start[N] != d->n_funcs)
-    return fail(PBN_EINVAL, "node_func_start must span 0..n_funcs");
-  std::vector<FuncRec> recs(d->n_funcs);
-  for (int i = 0; i < N; ++i) {
-    const int f0 = d->node_func_start[i], f1 = d->node_func_start[i + 1];
-    if (f1 <= f0 || f1 - f0 > PBN_MAX_FUNCS_PER_NODE)
-      return fail(PBN_EINVAL, "node " + std::to_string(i) + " needs 1..16 functions");
-    uint32_t prev = 0;
-    for (int f = f0; f < f1; ++f) {
-      const int k = d->func_arity[f];
-      if (k < 0 || k > PBN_MAX_ARITY) return fail(PBN_EINVAL, "function arity must be 0..4");
-      const uint32_t c = d->func_threshold[f];
-      if (c < prev || c > one) return fail(PBN_EINVAL, "thresholds must be non-decreasing and <= 2^prob_bits");
-      if (f == f1 - 1 && c != one) return fail(PBN_EINVAL, "last threshold of a node must be 2^prob_bits");
-      prev = c;
-      FuncRec& r = recs[f];
-      memset(&r, 0, sizeof r);
-      for (int j = 0; j < 4; ++j) {
-        int g = j < k ? d->func_inputs[4 * f + j] : 0;
-        if (g < 0 || g >= N + n_gates) return fail(PBN_EINVAL, "function input reference out of range");
-        r.in[j] = (uint32_t)(g < N ? g : 32 * W + (g - N));   // LDS plane index
-      }
-      const uint32_t T = d->func_table[f];
-      const uint32_t kmask = (k >= 5) ? 0xFFFFFFFFu : ((1u << k) - 1u);
-      if (k < 5 && (T >> (1u << k)) != 0u && (1u << k) < 32)
-        return fail(PBN_EINVAL, "truth table has bits beyond 2^arity");
-      for (int m = 0; m < 8; ++m) {
-        const uint32_t lo = (T >> ((2u * m) & kmask)) & 1u;        // x0 = 0
-        const uint32_t hi = (T >> ((2u * m + 1u) & kmask)) & 1u;   // x0 = 1
-        r.leaf[8 + m] = lo ? 0xFFFFFFFFu : 0u;
-        r.leaf[m] = (lo ^ hi) ? 0xFFFFFFFFu : 0u;
-      }
-      r.thr = c;
-    }
-  }
-  // attractors
-  const int A = d->n_attractors;
-  const int S = A ? d->n_attractor_states : 0;
-  std::vector<std::vector<uint32_t>> states;
-  std::vector<uint32_t> ids;
-  if (A) {
-    if (!d->attractor_start || !d->attractor_states) return fail(PBN_EINVAL, "null attractor tables");
-    if (d->attractor_start[0] != 0 || d->attractor_start[A] != S) return fail(PBN_EINVAL, "bad attractor_start");
-    for (int at = 0; at < A; ++at) {
-      if (d->attractor_start[at + 1] <= d->attractor_start[at]) return fail(PBN_EINVAL, "empty attractor");
-      for (int k = d->attractor_start[at]; k < d->attractor_start[at + 1]; ++k) {
-        states.emplace_back(d->attractor_states + (size_t)k * W, d->attractor_states + (size_t)k * W + W);
-        ids.push_back((uint32_t)at);
-      }
-    }
-  }
-  pbn_net* net = new pbn_net();
-  net->n_nodes = N;
-  net->W = W;
-  net->B = d->prob_bits;
-  net->horizon = d->horizon;
-  net->n_attr = A;
-  net->n_states = S;
-  net->cdf_len = 32;
-  while (net->cdf_len < N) net->cdf_len <<= 1;
-  std::vector<uint32_t> hash_img;
-  if (A) {
-    if (!build_hash(states, ids, W, &net->hash_bits, &net->hash_probes, net->hash_mult, &hash_img)) {
-      free_net(net);
-      return fail(PBN_EINVAL, "too many attractor states for the LDS hash");
-    }
-  }
-  // LDS table image: cdf[cdf_len] | reward[N+1][4] | hash[1 << bits][HashStride<W>]
-  std::vector<uint32_t> tab(net->cdf_len, 0xFFFFFFFFu);
-  for (int m = 0; m < N; ++m) tab[m] = d->perturb_cdf[m];
-  for (int m = 1; m < N; ++m)
-    if (tab[m] < tab[m - 1]) {
-      free_net(net);
-      return fail(PBN_EINVAL, "perturb_cdf must be non-decreasing");
-    }
-  // reward rows by popcount(flipmask): {none, wrong attractor, target, 0} (one 16-byte read)
-  for (int pc = 0; pc <= N; ++pc)
-    for (int c = 0; c < 4; ++c) {
-      uint32_t u = 0;
-      if (c < 3) memcpy(&u, &d->reward_table[c * (N + 1) + pc], 4);
-      tab.push_back(u);
-    }
-  tab.insert(tab.end(), hash_img.begin(), hash_img.end());
-  // attractor start[A+1] | states[S][W], read by autoreset in the wave kernel
-  net->att_off = (int)tab.size();
-  if (A) {
-    for (int k = 0; k <= A; ++k) tab.push_back((uint32_t)d->attractor_start[k]);
-    tab.insert(tab.end(), d->attractor_states, d->attractor_states + (size_t)S * W);
-  }
-  while (tab.size() & 3) tab.push_back(0u);  // 16-byte aligned uint4 selectors
-  for (int i = 0; i < N; ++i)
-    net->max_nf = std::max(net->max_nf, d->node_func_start[i + 1] - d->node_func_start[i]);
-  // records per node in the LDS image: no kernel reads record q >= max_nf (the chains stop at a
-  // node's function count, the padded ones at max_nf), so the image holds min(max_nf, kNodeRecs)
-  // of them at the [kNodeRecs]-layout's strides (pbn70: 4.6 KB less LDS per block)
-  const int Q = std::min(std::max(net->max_nf, 1), kNodeRecs);
-  // leaf selectors of the first Q functions of every node, uint4 [Q][2][32W]
-  // (lane-consecutive 16-byte reads); see eval_sel
-  net->sel_off = (int)tab.size();
-  {
-    std::vector<uint32_t> sel((size_t)Q * 2 * 32 * W * 4, 0x0C0C0C0Cu);
-    for (int i = 0; i < N; ++i) {
-      const int f0 = d->node_func_start[i], nf = d->node_func_start[i + 1] - f0;
-      // records beyond a node's last function (up to Q) repeat the last one: the
-      // pipelined kernel's chain then needs no per-lane function count (x = lt ? f : x with
-      // f == x is x)
-      for (int q = 0; q < Q; ++q) {
-        const int qf = std::min(q, nf - 1);
-        const uint32_t T = d->func_table[f0 + qf];
-        const int k = d->func_arity[f0 + qf];
-        for (int mm = 0; mm < 8; ++mm) {
-          // table bit of input index m (missing inputs read plane 0 but do not matter)
-          auto bit = [&](uint32_t m) { return (T >> (k >= 5 ? m : (m & ((1u << k) - 1u)))) & 1u; };
-          const uint32_t l0 = bit(2u * mm), l1 = bit(2u * mm + 1u);
-          uint32_t word = 0;
-          for (uint32_t j = 0; j < 4; ++j) {
-            const uint32_t b = (!l0 && !l1) ? 12u : (l0 && l1) ? 13u : (l1 ? j : 4u + j);
-            word |= b << (8 * j);
-          }
-          const int h = mm >> 2;
-          sel[(((size_t)q * 2 + h) * 32 * W + i) * 4 + (mm & 3)] = word;
-        }
-      }
-    }
-    tab.insert(tab.end(), sel.begin(), sel.end());
-  }
-  // threshold classes: the distinct values among the first kNodeRecs thresholds of all nodes;
-  // with at most kNodeRecs of them the kernels compare against wave-uniform digits
-  std::vector<uint32_t> cls_of((size_t)d->n_funcs, 0u);
-  {
-    std::vector<uint32_t> vals;
-    bool ok = true;
-    for (int i = 0; i < N && ok; ++i) {
-      const int f0 = d->node_func_start[i], nf = d->node_func_start[i + 1] - f0;
-      for (int q = 0; q < kNodeRecs && q < nf - 1; ++q) {
-        const uint32_t c = d->func_threshold[f0 + q];
-        auto it = std::find(vals.begin(), vals.end(), c);
-        if (it == vals.end()) {
-          if ((int)vals.size() == kNodeRecs) { ok = false; break; }
-          vals.push_back(c);
-          it = vals.end() - 1;
-        }
-        cls_of[f0 + q] = (uint32_t)(it - vals.begin());
-      }
-    }
-    net->n_cls = ok ? (int)vals.size() : 0;
-    for (int q = 0; q < kNodeRecs; ++q) net->uthr[q] = (ok && q < (int)vals.size()) ? vals[q] : 0u;
-    net->lq = std::max(net->max_nf - 1, 1);
-  }
-  std::vector<uint4> fcomp(d->n_funcs);
-  for (int f = 0; f < d->n_funcs; ++f) {
-    const FuncRec& r = recs[f];
-    uint32_t T4 = 0;
-    for (int mm = 0; mm < 8; ++mm) {
-      const uint32_t b0 = r.leaf[8 + mm] & 1u;               // value at x0 = 0
-      const uint32_t b1 = (r.leaf[8 + mm] ^ r.leaf[mm]) & 1u; // value at x0 = 1
-      T4 |= (b0 << (2 * mm)) | (b1 << (2 * mm + 1));
-    }
-    fcomp[f] = make_uint4(r.in[0] | (r.in[1] << 8) | (r.in[2] << 16) | (r.in[3] << 24), T4, r.thr, 0u);
-  }
-  std::vector<uint4> nrec((size_t)N * kNodeRecs, make_uint4(0, 0, 0, 0));
-  for (int i = 0; i < N; ++i) {
-    const int f0 = d->node_func_start[i], nf = d->node_func_start[i + 1] - f0;
-    for (int q = 0; q < kNodeRecs && q < nf; ++q) {
-      nrec[(size_t)i * kNodeRecs + q] = fcomp[f0 + q];
-      nrec[(size_t)i * kNodeRecs + q].y = cls_of[f0 + q];   // threshold class (the table lives in the selectors)
-    }
-    nrec[(size_t)i * kNodeRecs + 0].w = (uint32_t)nf;
-    nrec[(size_t)i * kNodeRecs + 1].w = (uint32_t)f0;
-  }
-  // the records in the LDS image too, record-major uint4 [Q][32W] (the pipelined
-  // kernel reads them per step instead of keeping them in VGPRs across its loop; lane = node,
-  // so consecutive lanes read consecutive 16-byte records: no LDS bank conflicts, where the
-  // node-major layout's 64-byte lane stride conflicted 4 ways)
-  net->nrec_off = (int)tab.size();
-  for (int q = 0; q < Q; ++q)
-    for (int i = 0; i < 32 * W; ++i) {
-      uint4 r4 = i < N ? nrec[(size_t)i * kNodeRecs + q] : make_uint4(0, 0, 0, 0);
-      if (i < N) {   // padded inputs as the selectors above (the .w metadata stays)
-        const int nf = d->node_func_start[i + 1] - d->node_func_start[i];
-        if (q >= nf) r4.x = nrec[(size_t)i * kNodeRecs + nf - 1].x;
-      }
-      if (W <= 2) r4.x *= 4u;   // plane byte offsets (every index < 64: no carry between bytes)
-      tab.push_back(r4.x); tab.push_back(r4.y); tab.push_back(r4.z); tab.push_back(r4.w);
-    }
-  // gate records by level: {input plane indices as bytes, 16-bit table (unused inputs
-  // replicated), output plane index 32W + g, 0}, then the level starts
-  net->n_gates = n_gates;
-  if (n_gates) {
-    int n_lv = 0;
-    for (int g = 0; g < n_gates; ++g) n_lv = std::max(n_lv, glevel[g]);
-    std::vector<int> order(n_gates);
-    for (int g = 0; g < n_gates; ++g) order[g] = g;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return glevel[x] < glevel[y]; });
-    net->gate_off = (int)tab.size();
-    std::vector<int> starts(n_lv + 1, 0);
-    for (int idx = 0; idx < n_gates; ++idx) {
-      const int g = order[idx], k = d->gate_arity[g];
-      uint32_t ins = 0;
-      for (int j = 0; j < k; ++j) {
-        const int r = d->gate_inputs[4 * g + j];
-        ins |= (uint32_t)(r < N ? r : 32 * W + (r - N)) << (8 * j);
-      }
-      const uint32_t T = d->gate_table[g];
-      const uint32_t kmask = (1u << k) - 1u;
-      uint32_t T16 = 0;
-      for (uint32_t m = 0; m < 16; ++m) T16 |= ((T >> (m & kmask)) & 1u) << m;
-      tab.push_back(ins); tab.push_back(T16); tab.push_back((uint32_t)(32 * W + g)); tab.push_back(0u);
-      starts[glevel[g]] = idx + 1;   // running end of each level (levels are contiguous)
-    }
-    net->glayer_off = (int)tab.size();
-    tab.push_back(0u);
-    for (int lv = 1; lv <= n_lv; ++lv) {
-      if (starts[lv] == 0) starts[lv] = starts[lv - 1];
-      tab.push_back((uint32_t)starts[lv]);
-    }
-    net->n_glayers = n_lv;
-  }
-  // gap bucket table (gap_lut): the smallest bucket width 2^shift, shift = 32 - k with
-  // k = 6..10, under which every bucket below C[N-1] holds at most one CDF threshold;
-  // none found (p tiny) -> the estimate / binary search paths
-  {
-    const double p = (double)d->perturb_cdf[0] / 4294967296.0;
-    const bool exact = p < 1e-6 || p > 0.5;
-    auto gap_at = [&](uint64_t u) {   // min{m : u < C[m-1]}, N+1 if none
-      int m = 1;
-      while (m <= N && (uint64_t)d->perturb_cdf[m - 1] <= u) ++m;
-      return m;
-    };
-    if (!exact) {
-      for (int k = 6; k <= 10 && !net->gap_nb; ++k) {
-        const int shift = 32 - k;
-        const uint64_t w = 1ull << shift;
-        const uint32_t nb = (uint32_t)(((uint64_t)d->perturb_cdf[N - 1]) >> shift) + 1u;   // buckets that can see a flip
-        bool ok = true;
-        std::vector<uint32_t> lut;
-        for (uint32_t b = 0; b < nb && ok; ++b) {
-          const int lo = gap_at((uint64_t)b * w), hi = gap_at((uint64_t)b * w + w - 1);
-          ok = hi - lo <= 1;
-          lut.push_back(lo <= N ? d->perturb_cdf[lo - 1] : 0xFFFFFFFFu);
-          lut.push_back((uint32_t)lo);
-        }
-        if (!ok) continue;
-        lut.push_back(0xFFFFFFFFu);   // sentinel: u >= C[N-1] -> gap N+1 (u = 2^32-1 gives N+2, also no flip)
-        lut.push_back((uint32_t)(N + 1));
-        while (tab.size() & 1) tab.push_back(0u);
-        net->gap_lut_off = (int)tab.size();
-        tab.insert(tab.end(), lut.begin(), lut.end());
-        net->gap_shift = shift;
-        net->gap_nb = (int)nb;
-      }
-    }
-  }
-  // the pipelined one-update kernel's threshold digit masks (single-word states), lane-major
-  // [32][sel_mask_stride(B)]: mask (i, q, d) = ~0 if bit B-1-d of node i's threshold q is set.  In
-  // the image, they arrive with the table copy; built by each block from the LDS records, they
-  // cost a second prologue barrier (0.48 us of a 20-step launch, DESIGN.md "Launch anatomy")
-  net->cm_off = 0;
-  if (W == 1) {
-    while (tab.size() & 3) tab.push_back(0u);
-    net->cm_off = (int)tab.size();
-    const int B = d->prob_bits, S = sel_mask_stride(B);
-    std::vector<uint32_t> cmv((size_t)32 * S, 0u);
-    for (int i = 0; i < N; ++i) {
-      const int f0 = d->node_func_start[i], nf = d->node_func_start[i + 1] - f0;
-      for (int q = 0; q < kNodeRecs - 1 && q < nf - 1; ++q) {
-        const uint32_t c = recs[f0 + q].thr;
-        for (int dd = 0; dd < B; ++dd) cmv[(size_t)i * S + q * B + dd] = ((c >> (B - 1 - dd)) & 1u) ? ~0u : 0u;
-      }
-    }
-    tab.insert(tab.end(), cmv.begin(), cmv.end());
-  }
-  while (tab.size() & 3) tab.push_back(0u);   // the kernels copy the image as uint4
-  net->tab_words = (int)tab.size();
-  net->n_funcs = d->n_funcs;
-  net->wave_words = (32 * W + n_gates + 3) & ~3;   // S planes (+ gate planes) per wave
-  {
-    const double p = (double)d->perturb_cdf[0] / 4294967296.0;
-    net->gap_exact = (p < 1e-6 || p > 0.5) ? 1 : (net->gap_nb ? 2 : 0);
-    net->inv_log2q = net->gap_exact ? 0.f : (float)(1.0 / log2(1.0 - p));
-  }
-  net->lds_wave = ((size_t)net->tab_words + (size_t)kWavesPerBlock * net->wave_words) * 4;
-  net->slot_words = (3 * W + 1) * 64 + net->lq * 64 * W;
-  // (the selection wave's threshold digit masks are part of the image: cm_off)
-  net->lds_pipe = ((size_t)net->tab_words + 64 * (size_t)W + 2 * (size_t)net->slot_words) * 4;
-  // compact records for the wave kernel: {inputs as bytes, 4-input truth table, threshold, 0}
-  net->wave1 = pick_wave<1>(W, d->prob_bits);
-  net->wave_lean = pick_wave<2>(W, d->prob_bits);
-  net->wave_settle = reinterpret_cast<StepFn>(pbn::settle_kernel(W, d->prob_bits, 0));
-  net->wave_settle_lean = reinterpret_cast<StepFn>(pbn::settle_kernel(W, d->prob_bits, 1));
-  net->settle_max = d->settle_max;
-  net->pipe_settle = net->max_nf <= kNodeRecs ? reinterpret_cast<StepFn>(pbn::settle_pipe_kernel(W, d->prob_bits))
-                                              : nullptr;
-  // pbn_rollout_settle: S planes [64W] | 2 slots {flip mask, perturbation mask, reset state [3W][64],
-  // reset target and action count [64], selection planes [lq][64W]} | C [parity][64]{t, k}
-  net->slot_words_settle = 192 * W + 64 + net->lq * 64 * W;
-  // + ctl [2][64] uint4 + the packed thresholds [lq][W][16]
-  // + the output rows [settle_stage_rows(W)][settle_row_words(W)], the stored-row counter [2] and
-  // the rows' output pointers (6 x 8 bytes)
-  net->lds_settle = ((size_t)net->tab_words + 64 * (size_t)W + 2 * (size_t)net->slot_words_settle + 512 +
-                     (((size_t)net->lq * W * 16 + 3) & ~(size_t)3) +
-                     (size_t)settle_stage_rows(W) * settle_row_words(W) + 2 + 12 + 2) * 4;
-  net->pipe = pick_pipe(W, d->prob_bits, net->max_nf > kNodeRecs);
-  net->reset = pick_reset(W);
-  // multiply-high divisors (exact for the operand ranges used: see actions_from_draw, autoreset)
-  net->n1_magic = (uint32_t)(((1ull << 32) + (uint64_t)N) / (uint64_t)(N + 1));
-  net->att_single = A >= 1 && S == A ? 1 : 0;
-  net->am1_magic = A >= 3 ? (uint32_t)(((1ull << 32) + (uint64_t)(A - 2)) / (uint64_t)(A - 1)) : 0u;   // 0: A - 1 == 1
-  net->x_mult = (uint64_t)(N + 1) * (uint64_t)(N + 1) * (uint64_t)(N + 1) * (A >= 2 ? (uint64_t)A * (uint64_t)(A - 1) : 1ull);
-  if (const char* env = getenv("PBN_ROLL")) {
-    if (!strcmp(env, "lean")) net->force_roll = 2;
-    if (!strcmp(env, "pipe")) net->force_roll = 3;
-  }
-  // the settle law's per-env selection thresholds (settle_lt_word): node i, threshold q <
-  // nf_i - 1 as c << (16 - B), 65536 (always) past a node's last function and past the network
-  std::vector<uint32_t> sthr((size_t)net->lq * 32 * W, 65536u);
-  for (int i = 0; i < N; ++i) {
-    const int f0 = d->node_func_start[i], nf = d->node_func_start[i + 1] - f0;
-    for (int q = 0; q < nf - 1 && q < net->lq; ++q)
-      sthr[(size_t)q * 32 * W + i] = d->func_threshold[f0 + q] << (16 - d->prob_bits);
-  }
-  // packed biased node pairs for settle_lt_word_pk, exact when no compared threshold is 65536
-  std::vector<uint32_t> sthr_pk((size_t)net->lq * W * 16);
-  net->settle_pk = 1;
-  for (int q = 0; q < net->lq; ++q)
-    for (int i = 0; i < 32 * W; i += 2) {
-      uint32_t c[2];
-      for (int h = 0; h < 2; ++h) {
-        const int ii = i + h;
-        const bool real = ii < N && q < d->node_func_start[ii + 1] - d->node_func_start[ii] - 1;
-        const uint32_t v = sthr[(size_t)q * 32 * W + ii];
-        if (real && v > 65535u) net->settle_pk = 0;
-        c[h] = std::min(v, 65535u) ^ 0x8000u;
-      }
-      sthr_pk[((size_t)q * W + i / 32) * 16 + (i % 32) / 2] = c[0] | (c[1] << 16);
-    }
-  std::vector<uint32_t> att_first((size_t)A * W);
-  for (int t = 0; t < A; ++t)
-    for (int w = 0; w < W; ++w) att_first[(size_t)t * W + w] = d->attractor_states[(size_t)d->attractor_start[t] * W + w];
-  int rc;
-  if (hipGetDevice(&net->device) != hipSuccess) {
-    free_net(net);
-    return fail(PBN_EDEVICE, "no HIP device");
-  }
+  pbn::NetImage im;
+  std::string err;
+  int rc = pbn::compile_net(d, &im, &err);
+  if (rc) return fail(rc, err);
+  auto net = std::make_unique<pbn_net>();
+  if (hipGetDevice(&net->device) != hipSuccess) return fail(PBN_EDEVICE, "no HIP device");
   if (hipDeviceGetAttribute(&net->n_cus, hipDeviceAttributeMultiprocessorCount, net->device) != hipSuccess ||
       net->n_cus <= 0)
     net->n_cus = 256;
-  if ((rc = upload(&net->d_fcompact, fcomp.data(), fcomp.size())) ||
-      (rc = upload(&net->d_nrec, nrec.data(), nrec.size())) ||
-      (rc = upload(&net->d_sthr, sthr.data(), sthr.size())) ||
-      (rc = upload(&net->d_sthr_pk, sthr_pk.data(), sthr_pk.size())) ||
-      (rc = upload(&net->d_tab, tab.data(), tab.size())) ||
-      (rc = upload(&net->d_att_start, A ? d->attractor_start : nullptr, (size_t)A + 1)) ||
-      (rc = upload(&net->d_att_states, S ? d->attractor_states : nullptr, (size_t)S * W)) ||
-      (rc = upload(&net->d_att_first, A ? att_first.data() : nullptr, (size_t)A * W))) {
-    free_net(net);
-    return rc;
-  }
-  for (int ti = 0; ti < 6; ++ti) {
-    const StepFn fns[6] = {net->wave_settle, net->wave_settle_lean, net->wave_lean, net->wave1, net->pipe,
-                           net->pipe_settle};
-    const StepFn fn = fns[ti];
-    const size_t bytes = ti == 5 ? net->lds_settle : (ti == 4 ? net->lds_pipe : net->lds_wave);
-    if (!fn || bytes > 160 * 1024) continue;  // variant unusable for this net; never picked
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)bytes) != hipSuccess) {
-      free_net(net);
-      return fail(PBN_EDEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-    }
-  }
-  if (net->lds_wave > 160 * 1024) {
-    free_net(net);
-    return fail(PBN_EINVAL, "LDS budget exceeded");
-  }
-  *out = net;
+  if ((rc = upload_image(im, d, net.get()))) return rc;
+  set_base(im, net.get());
+  pick_kernels(im, net.get());
+  if ((rc = raise_lds_limits(*net))) return rc;
+  if (net->route.lds_wave > kLdsDeviceBytes) return fail(PBN_EINVAL, "LDS budget exceeded");
+  *out = net.release();
   return PBN_OK;
 }
 
@@ -793,8 +375,7 @@ int pbn_debug_set_stamps(unsigned long long* d_buf) {
 #endif
 
 int pbn_net_destroy(pbn_net* net) {
-  if (!net) return PBN_OK;
-  free_net(net);
+  delete net;
   return PBN_OK;
 }
 
@@ -816,61 +397,26 @@ static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 // The launch arguments every step kernel shares: the net's tables and encodings, the key and
 // the env range (the caller adds its buffers, mode and step count)
-static void fill_args(const pbn_net* net, StepArgs* p, uint64_t seed, uint64_t step, uint64_t env_offset,
+static void fill_args(const pbn_net* net, StepArgs* a, uint64_t seed, uint64_t step, uint64_t env_offset,
                       int64_t n_envs) {
-  StepArgs& a = *p;
-  memset(&a, 0, sizeof a);
-  a.tab = net->d_tab;
-  a.att_start = net->d_att_start;
-  a.att_states = net->d_att_states;
-  a.seed = seed;
-  a.step = step;
-  a.env_offset = env_offset;
-  a.n_envs = n_envs;
-  a.n_groups = (n_envs + 31) / 32;
-  a.n_steps = 1;
-  a.n_nodes = net->n_nodes;
-  a.n_attr = net->n_attr;
-  a.horizon = net->horizon;
-  a.cdf_len = net->cdf_len;
-  a.hash_bits = net->n_attr ? net->hash_bits : 0;
-  a.hash_probes = net->hash_probes;
-  a.tab_words = net->tab_words;
-  a.n_states = net->n_states;
-  a.att_off = net->att_off;
-  a.sel_off = net->sel_off;
-  a.nrec_off = net->nrec_off;
-  a.cm_off = net->cm_off;
-  a.n_cls = net->n_cls;
-  a.max_nf = net->max_nf;
-  a.lq = net->lq;
-  a.slot_words = net->slot_words;
-  a.gate_off = net->gate_off;
-  a.glayer_off = net->glayer_off;
-  a.n_glayers = net->n_glayers;
-  memcpy(a.uthr, net->uthr, sizeof a.uthr);
-  memcpy(a.hash_mult, net->hash_mult, sizeof a.hash_mult);
-  a.prob_bits = net->B;
-  a.n_funcs = net->n_funcs;
-  a.wave_words = net->wave_words;
-  a.gap_exact = net->gap_exact;
-  a.gap_lut_off = net->gap_lut_off;
-  a.gap_shift = net->gap_shift;
-  a.gap_nb = net->gap_nb;
-  a.inv_log2q = net->inv_log2q;
-  a.fcompact = net->d_fcompact;
-  a.nrec = net->d_nrec;
-  a.sthr = net->d_sthr;
-  a.sthr_pk = net->d_sthr_pk;
-  a.settle_pk = net->settle_pk;
-  a.n1_magic = net->n1_magic;
-  a.att_single = net->att_single;
-  a.am1_magic = net->am1_magic;
-  a.x_mult = net->x_mult;
-  a.settle_max = net->settle_max;
+  *a = net->base;
+  a->seed = seed;
+  a->step = step;
+  a->env_offset = env_offset;
+  a->n_envs = n_envs;
+  a->n_groups = (n_envs + 31) / 32;
 #ifdef PBN_STAMPS
-  a.stamps = g_stamps;
+  a->stamps = g_stamps;
 #endif
+}
+
+// one launch of the kernel r names over a's groups
+static int launch(const pbn_net* net, const Route& r, StepArgs a, int threads, void* stream) {
+  if (r.kernel == kPipeSettle) a.slot_words = net->slot_words_settle;
+  const unsigned blocks = (unsigned)((a.n_groups + r.groups_per_block - 1) / r.groups_per_block);
+  hipLaunchKernelGGL(net->kernels[r.kernel], dim3(blocks), dim3(threads), r.lds_bytes, (hipStream_t)stream, a);
+  HIP_OK(hipGetLastError());
+  return PBN_OK;
 }
 
 int pbn_reset(pbn_net* net, uint64_t seed, uint64_t step, uint64_t env_offset, int64_t n_envs,
@@ -881,9 +427,9 @@ int pbn_reset(pbn_net* net, uint64_t seed, uint64_t step, uint64_t env_offset, i
   if (!d_state || !d_target || !d_t) return fail(PBN_EINVAL, "null buffer");
   const int threads = 256;
   const unsigned blocks = (unsigned)((n_envs + threads - 1) / threads);
-  hipLaunchKernelGGL(net->reset, dim3(blocks), dim3(threads), 0, (hipStream_t)stream, net->d_att_start,
-                     net->d_att_states, net->n_attr, net->n_states, net->n_nodes, seed, step, env_offset, n_envs, d_state,
-                     d_target, d_t);
+  const StepArgs& b = net->base;
+  hipLaunchKernelGGL(net->reset, dim3(blocks), dim3(threads), 0, (hipStream_t)stream, b.att_start, b.att_states,
+                     b.n_attr, b.n_states, b.n_nodes, seed, step, env_offset, n_envs, d_state, d_target, d_t);
   HIP_OK(hipGetLastError());
   return PBN_OK;
 }
@@ -916,10 +462,9 @@ static int step_impl(pbn_net* net, uint64_t seed, uint64_t step, const uint64_t*
   a.reward = d_reward;
   a.flags = d_flags;
   a.mode = (int)mode;
-  if (net->lds_wave > 160 * 1024) return fail(PBN_EINVAL, "network too large for the step kernel's LDS");
   if (ring) {
     const pbn_ring_store& r = *ring;
-    if (net->settle_max >= 2) return fail(PBN_EINVAL, "pbn_step_dev_store: the one-update law only (settle_max < 2)");
+    if (net->route.settle) return fail(PBN_EINVAL, "pbn_step_dev_store: the one-update law only (settle_max < 2)");
     if (r.capacity < n_envs) return fail(PBN_EINVAL, "pbn_ring_store: capacity < n_envs");
     if (r.n_branches < 1 || r.n_branches > kRingMaxK) return fail(PBN_EINVAL, "pbn_ring_store: n_branches 1..8");
     if (!r.d_pos || ((uintptr_t)r.d_pos & 7u) || !r.d_state || !r.d_next_state || !r.d_target || !r.d_reward ||
@@ -943,19 +488,8 @@ static int step_impl(pbn_net* net, uint64_t seed, uint64_t step, const uint64_t*
   // its own update sequence and an update is one pipeline iteration, against the wave kernel's
   // variant 3, whose wave runs every update of its slowest env as a serial chain (VERDICT r05
   // next 2).  Ragged env counts, gates, PBN_ROLL=lean: the wave kernel.
-  if (net->settle_max >= 2 && !(n_envs & 31) && net->pipe_settle && !net->n_gates &&
-      net->lds_settle <= 64 * 1024 && net->force_roll != 2) {
-    a.slot_words = net->slot_words_settle;
-    const int64_t pblocks = (a.n_groups + 1) / 2;
-    hipLaunchKernelGGL(net->pipe_settle, dim3((unsigned)pblocks), dim3(192), net->lds_settle, (hipStream_t)stream, a);
-    HIP_OK(hipGetLastError());
-    return PBN_OK;
-  }
-  const unsigned blocks = (unsigned)((a.n_groups + kWavesPerBlock - 1) / kWavesPerBlock);  // one wave per group
-  const StepFn fn = net->settle_max >= 2 ? net->wave_settle : net->wave1;
-  hipLaunchKernelGGL(fn, dim3(blocks), dim3(64 * kWavesPerBlock), net->lds_wave, (hipStream_t)stream, a);
-  HIP_OK(hipGetLastError());
-  return PBN_OK;
+  const Route r = route_launch(net->route, false, !(n_envs & 31));
+  return launch(net, r, a, r.threads, stream);
 }
 
 int pbn_step(pbn_net* net, uint64_t seed, uint64_t step, uint64_t env_offset, int64_t n_envs, uint32_t mode,
@@ -1019,7 +553,6 @@ static int rollout_impl(pbn_net* net, uint64_t seed, uint64_t step, uint64_t env
   if (n_envs == 0 || n_steps == 0) return after.finish(PBN_OK);
   if (mode & ~(PBN_MODE_AUTORESET | PBN_MODE_RANDOM_ACTIONS)) return fail(PBN_EINVAL, "unknown mode bits");
   if (!d_state || !d_flipmask || !d_target || !d_t || !d_reward || !d_flags) return fail(PBN_EINVAL, "null buffer");
-  if (net->lds_wave > 160 * 1024) return fail(PBN_EINVAL, "network too large for the rollout kernel's LDS");
   StepArgs a;
   fill_args(net, &a, seed, step, env_offset, n_envs);
   a.state = d_state;
@@ -1037,20 +570,12 @@ static int rollout_impl(pbn_net* net, uint64_t seed, uint64_t step, uint64_t env
   // the pipelined kernels for every network they support (they beat the one-wave-per-group
   // rollout at every measured size: profiles/r01_sweep_pbn28_variants_v4.jsonl); networks
   // with gates (lowered wide functions) run the wave kernel.  PBN_ROLL=lean|pipe forces one.
-  const bool settle = net->settle_max >= 2;
-  bool pipe = (settle ? net->lds_settle : net->lds_pipe) <= 64 * 1024 && !net->n_gates && (!settle || net->pipe_settle);
-  if (net->force_roll) pipe = net->force_roll == 3 && !net->n_gates && (!settle || net->pipe_settle);
-  if (pipe) {   // one block of three waves per pair of groups
-    const int64_t pblocks = (a.n_groups + 1) / 2;
-    if (settle) {
-      a.slot_words = net->slot_words_settle;
-      hipLaunchKernelGGL(net->pipe_settle, dim3((unsigned)pblocks), dim3(192), net->lds_settle,
-                         (hipStream_t)stream, a);
-      HIP_OK(hipGetLastError());
-      return after.finish(PBN_OK);
-    }
+  const Route r = route_launch(net->route, true, true);
+  int threads = r.threads;
+  if (r.kernel == kPipe) {
     // the one-update law applies exactly one synchronous update per env-step
     if (d_updates) HIP_OK(hipMemsetD16Async(d_updates, 1, (size_t)n_steps * (size_t)n_envs, (hipStream_t)stream));
+    const int64_t pblocks = (a.n_groups + 1) / 2;
     a.sel_prio = pblocks <= 4 * (int64_t)net->n_cus ? 1 : 0;
     if (cp_bytes > 0) {   // the ride-along copy: a fourth wave per block
       a.cp_src = cp_src;
@@ -1067,17 +592,10 @@ static int rollout_impl(pbn_net* net, uint64_t seed, uint64_t step, uint64_t env
       // rate, pbn70 x 1M: 0.65 -> 0.73x; profiles/r05_zj_ab.json)
       if (pblocks > 4 * (int64_t)net->n_cus) a.cp_u = 0;
       copy_after = false;
+      threads += 64;
     }
-    hipLaunchKernelGGL(net->pipe, dim3((unsigned)pblocks), dim3(a.cp_n16 ? 256 : 192), net->lds_pipe,
-                       (hipStream_t)stream, a);
-    HIP_OK(hipGetLastError());
-    return after.finish(PBN_OK);
   }
-  const unsigned blocks = (unsigned)((a.n_groups + kWavesPerBlock - 1) / kWavesPerBlock);  // one wave per group
-  hipLaunchKernelGGL(net->settle_max >= 2 ? net->wave_settle_lean : net->wave_lean, dim3(blocks),
-                     dim3(64 * kWavesPerBlock), net->lds_wave, (hipStream_t)stream, a);
-  HIP_OK(hipGetLastError());
-  return after.finish(PBN_OK);
+  return after.finish(launch(net, r, a, threads, stream));
 }
 
 extern "C" {

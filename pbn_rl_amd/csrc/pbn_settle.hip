@@ -7,32 +7,24 @@
 namespace {
 
 template <int V>
-void* pick_settle(int W, int B) {
-#define PBN_SETTLE_CASE(w, b) \
-  if (W == w && B == b) return reinterpret_cast<void*>(&pbn_step_wave<w, b, V>);
-#define PBN_SETTLE_W(w) PBN_SETTLE_CASE(w, 4) PBN_SETTLE_CASE(w, 8) PBN_SETTLE_CASE(w, 12) PBN_SETTLE_CASE(w, 16)
-  PBN_SETTLE_W(1) PBN_SETTLE_W(2) PBN_SETTLE_W(3) PBN_SETTLE_W(4)
-#undef PBN_SETTLE_W
-#undef PBN_SETTLE_CASE
-  return nullptr;
-}
-
-void* pick_settle_pipe(int W, int B) {
-#define PBN_SETTLE_CASE(w, b) \
-  if (W == w && B == b) return reinterpret_cast<void*>(&pbn_rollout_settle<w, b>);
-#define PBN_SETTLE_W(w) PBN_SETTLE_CASE(w, 4) PBN_SETTLE_CASE(w, 8) PBN_SETTLE_CASE(w, 12) PBN_SETTLE_CASE(w, 16)
-  PBN_SETTLE_W(1) PBN_SETTLE_W(2) PBN_SETTLE_W(3) PBN_SETTLE_W(4)
-#undef PBN_SETTLE_W
-#undef PBN_SETTLE_CASE
-  return nullptr;
+StepFn pick_settle(int W, int B) {
+  return step_kernel_for(W, B, [](auto w, auto b) -> StepFn {
+    return pbn_step_wave<decltype(w)::value, decltype(b)::value, V>;
+  });
 }
 
 }  // namespace
 
 namespace pbn {
 
-void* settle_kernel(int W, int B, int lean) { return lean ? pick_settle<4>(W, B) : pick_settle<3>(W, B); }
+void* settle_pipe_kernel(int W, int B) {
+  return reinterpret_cast<void*>(step_kernel_for(W, B, [](auto w, auto b) -> StepFn {
+    return pbn_rollout_settle<decltype(w)::value, decltype(b)::value>;
+  }));
+}
 
-void* settle_pipe_kernel(int W, int B) { return pick_settle_pipe(W, B); }
+void* settle_kernel(int W, int B, int lean) {
+  return reinterpret_cast<void*>(lean ? pick_settle<4>(W, B) : pick_settle<3>(W, B));
+}
 
 }  // namespace pbn

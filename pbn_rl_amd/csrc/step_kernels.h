@@ -9,8 +9,11 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "../../include/pbn_env.h"
 #include "bitslice.h"
+#include "net_layout.h"
 #include "philox.h"
 
 using pbn::bfi;
@@ -18,20 +21,7 @@ using pbn::Word4;
 
 namespace {
 
-constexpr int kFuncRecWords = 24;  // in[4], leaf[16], thr, pad[3]
-constexpr int kNodeRecs = 4;       // compact records prefetched per node by the wave kernel
 constexpr int kStatePrio = 2;      // s_setprio of the pipelined rollout's state wave
-
-constexpr int kWavesPerBlock = 4;  // wave kernel: waves (32-env groups) per block, sharing one LDS table image
-constexpr int kMaxHashBits = 12;
-
-struct FuncRec {   // host-side function record (validation, leaf tables for the selectors)
-  uint32_t in[4];      // input node index per mux level (padded with 0)
-  uint32_t leaf[16];   // leaf[m] = d_m (x0 mask), leaf[8+m] = beta_m
-  uint32_t thr;        // cumulative selection threshold c_f (prob_bits units)
-  uint32_t pad[3];
-};
-static_assert(sizeof(FuncRec) == kFuncRecWords * 4, "FuncRec layout");
 
 struct StepArgs {
   const uint32_t* tab;          // packed LDS image (cdf | reward | hash)
@@ -301,7 +291,7 @@ __device__ __forceinline__ void copy_image(uint32_t* L, const StepArgs& a) {
 // of two, so that one probe is one ds_read_b64 (W = 1) or ds_read_b128 (W = 2, 3)
 template <int W>
 struct HashStride {
-  static constexpr int value = W == 1 ? 2 : (W <= 3 ? 4 : 8);
+  static constexpr int value = hash_stride(W);
 };
 
 // attractor id of the state sp at slot s, or -1
@@ -383,14 +373,7 @@ __device__ __forceinline__ uint32_t less_than(const uint32_t (&dig)[16], uint32_
 
 // less_than with the threshold's digit masks read from LDS: cmq[d * stride] = ~0 if bit
 // (B-1-d) of the threshold is set, else 0 (built once per block; saves a v_bfe per digit)
-// pbn_rollout_pipe's threshold digit masks, lane-major: node i's masks of threshold q, digit d at
-// cm[i * S + q * B + d], S = sel_mask_stride(B) words: four masks are one 16-byte ds_read_b128,
-// and S = 4 x odd puts the 16 lanes of each read quarter on distinct 4-bank groups (conflict
-// free; the node-major layout before it read two masks per ds_read2_b32, at twice the LDS-array
-// cycles per mask)
-__host__ __device__ constexpr int sel_mask_stride(int B) {
-  return 4 * (((3 * B + 3) / 4) | 1);
-}
+// (the masks' layout: sel_mask_stride, net_layout.h)
 template <int B>
 __device__ __forceinline__ uint32_t less_than_cm4(const uint32_t (&dig)[16], const uint32_t* __restrict__ cmq) {
   const uint4* c4 = reinterpret_cast<const uint4*>(cmq);
@@ -1006,7 +989,7 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) pbn_step_wave(StepArgs a)
   constexpr int NUP = W * (CPN - H);       // upper list: SEL(c >= H)
   constexpr int IT = NLO > NUP ? NLO : NUP;
   constexpr int UPC = (CPN - H) > 0 ? (CPN - H) : 1;  // divisor guard (B = 4: no upper calls)
-  extern __shared__ uint32_t smem[];
+  extern __shared__ uint32_t smem[];   // carved below; sized by wave_lds_words (net_layout.h)
   PBN_STAMP(0);
   const int lane = threadIdx.x & 63;
   const int wv = threadIdx.x >> 6;
@@ -1451,7 +1434,7 @@ __device__ __forceinline__ uint32_t chain_padded(const uint4* __restrict__ rec, 
 template <int W, int B, bool MANY>
 __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a) {
   constexpr int CPN = B / 4;              // selection calls per node
-  extern __shared__ uint32_t smem[];
+  extern __shared__ uint32_t smem[];   // carved below; sized by pipe_lds_words (net_layout.h)
   const int lane = threadIdx.x & 63;
   const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: scalar branches
   // the state wave bounds every iteration: let it win VALU issue against the RNG waves of
@@ -1491,7 +1474,7 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
   const uint32_t* htab = L + a.cdf_len + 4 * (N + 1);
   const uint4* selq = reinterpret_cast<const uint4*>(L + a.sel_off);
   uint32_t* Sg = smem + a.tab_words + half * 32 * W;   // this half's group
-  uint32_t* slots = smem + a.tab_words + 2 * 32 * W;
+  uint32_t* slots = smem + a.tab_words + pipe_planes_words(W);
   uint32_t st[W];
   uint32_t tt0 = 0, tg0 = 0;
 #pragma unroll
@@ -2114,8 +2097,7 @@ constexpr uint32_t kNoUpd = 0xFFFFFFFFu;
 // waits (its update is produced and not applied), so a row is never reused before it is stored.
 // Row layout (words): final [W][64] | obs [W][64] | flip mask [W][64] | reward [64] | flags
 // [64 bytes] | update counts [64 u16].
-__host__ __device__ constexpr int settle_stage_rows(int W) { return W == 1 ? 16 : (W == 2 ? 8 : 4); }
-__host__ __device__ constexpr int settle_row_words(int W) { return 3 * 64 * W + 64 + 16 + 32; }
+// (settle_stage_rows, settle_row_words: net_layout.h, with the kernel's whole LDS carving.)
 struct StageOut {   // the output pointers the row stores use, copied to LDS at kernel start
   uint32_t* final_state;
   uint32_t* obs;
@@ -2124,6 +2106,7 @@ struct StageOut {   // the output pointers the row stores use, copied to LDS at 
   uint8_t* flags;
   uint16_t* updates;
 };
+static_assert(sizeof(StageOut) == kStageOutWords * 4, "StageOut is part of settle_lds_words");
 constexpr uint32_t kSettleStampIt = 300;   // stamps build: the iteration the settle kernel clocks
 
 // The per-env update plan of pbn_rollout_settle, in that env's lane of every wave (VGPRs; the
@@ -2148,7 +2131,7 @@ struct EnvPlan {
 template <int W, int B>
 __global__ void __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(4, 8)))
 pbn_rollout_settle(StepArgs a) {
-  extern __shared__ uint32_t smem[];
+  extern __shared__ uint32_t smem[];   // carved below; sized by settle_lds_words (net_layout.h)
   const int lane = threadIdx.x & 63;
   const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (role == 0) __builtin_amdgcn_s_setprio(kStatePrio);
@@ -2181,7 +2164,7 @@ pbn_rollout_settle(StepArgs a) {
   uint32_t* Sg = smem + a.tab_words + half * 32 * W;
   // slot (per iteration parity), env-major [.][64]: flip mask [W] | perturbation mask [W] | k = 0:
   // reset state [W] | k = 0: {reset target, action count} | selection planes [lq][2][32W]
-  uint32_t* slots = smem + a.tab_words + 2 * 32 * W;
+  uint32_t* slots = smem + a.tab_words + pipe_planes_words(W);
   constexpr int kGP = 64 * W, kRS = 128 * W, kIN = 192 * W, kLT = 192 * W + 64;
   // [parity][64]{C.t, C.k, R.t, R.k}: per env the state wave's decision C and the plan R of the
   // next iteration (EnvPlan, derived once by the state wave for all three)
@@ -2192,7 +2175,7 @@ pbn_rollout_settle(StepArgs a) {
   }
   // the packed thresholds (settle_pk), [lq][W][16] words after ctl: the selection wave reads them
   // by broadcast LDS reads
-  uint32_t* thr_l = reinterpret_cast<uint32_t*>(ctl + 128);
+  uint32_t* thr_l = reinterpret_cast<uint32_t*>(ctl + kSettleCtlVecs);
   if (a.settle_pk) {
     for (int i = (int)threadIdx.x; i < lq * W * 16; i += (int)blockDim.x) thr_l[i] = a.sthr_pk[i];
   }
@@ -2201,9 +2184,9 @@ pbn_rollout_settle(StepArgs a) {
   // wave in iteration i + 1)
   constexpr int R = settle_stage_rows(W), RW = settle_row_words(W);
   constexpr int kSF = 0, kSO = 64 * W, kSM = 128 * W, kSR = 192 * W, kSFL = 192 * W + 64, kSU = 192 * W + 80;
-  uint32_t* stg = thr_l + ((lq * W * 16 + 3) & ~3);
-  uint32_t* stg_base = stg + R * RW;
-  uint64_t* stg_out = reinterpret_cast<uint64_t*>(stg_base + 2);   // the row stores' pointers (StageOut)
+  uint32_t* stg = thr_l + settle_thr_words(W, lq);
+  uint32_t* stg_base = stg + settle_rows_words(W);
+  uint64_t* stg_out = reinterpret_cast<uint64_t*>(stg_base + kSettleRowCounterWords);   // the row stores' pointers (StageOut)
   if (threadIdx.x < 2) stg_base[threadIdx.x] = 0u;
   if (threadIdx.x == 0) {
     stg_out[0] = reinterpret_cast<uint64_t>(a.final_state);
@@ -2806,6 +2789,39 @@ __global__ void __launch_bounds__(256) pbn_reset_kernel(const int32_t* __restric
   for (int w = 0; w < W; ++w) state[(size_t)w * n + i] = ns[w];
   target[i] = (uint8_t)nt;
   t[i] = 0;
+}
+
+// The (W, B) dispatcher: the step kernels are instantiated for 1..4 state words and 4, 8, 12 or
+// 16 probability bits.  make(w, b) receives the pair as std::integral_constant values and
+// returns the host stub of its instance; nullptr for any other pair.  (for_state_words and
+// for_prob_bits are its halves, for a caller that chooses something between the two.)
+using StepFn = void (*)(StepArgs);
+
+template <typename F>
+StepFn for_state_words(int W, F f) {
+  switch (W) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+  }
+  return nullptr;
+}
+
+template <typename F>
+StepFn for_prob_bits(int B, F f) {
+  switch (B) {
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 12: return f(std::integral_constant<int, 12>{});
+    case 16: return f(std::integral_constant<int, 16>{});
+  }
+  return nullptr;
+}
+
+template <typename Make>
+StepFn step_kernel_for(int W, int B, Make make) {
+  return for_state_words(W, [&](auto w) { return for_prob_bits(B, [&](auto b) { return make(w, b); }); });
 }
 
 }  // namespace

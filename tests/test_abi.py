@@ -88,6 +88,109 @@ def test_create_rejects_bad_thresholds(lib):
     assert rc == -22 and "threshold" in err
 
 
+def _first_func(spec, min_funcs=1, min_arity=0):
+    """(node, first function index) of the first node with at least min_funcs functions whose
+    first function has at least min_arity inputs."""
+    start, arity = spec.arrays["node_func_start"], spec.arrays["func_arity"]
+    for i in range(spec.n):
+        if start[i + 1] - start[i] >= min_funcs and arity[start[i]] >= min_arity:
+            return i, int(start[i])
+    raise AssertionError("no such node")
+
+
+def _gate_arity(spec):
+    spec.arrays["gate_arity"][0] = 5
+
+
+def _gate_table_bits(spec):
+    spec.arrays["gate_table"][0] |= 1 << 16
+
+
+def _gate_input_order(spec):
+    g = int((spec.arrays["gate_arity"] >= 1).argmax())
+    spec.arrays["gate_inputs"][4 * g] = spec.n + g   # itself
+
+
+def _func_start_span(spec):
+    spec.arrays["node_func_start"][0] = 1
+
+
+def _func_count(spec):
+    spec.arrays["node_func_start"][1] = 0
+
+
+def _func_arity(spec):
+    spec.arrays["func_arity"][0] = 5
+
+
+def _thresholds_decrease(spec):
+    _, f0 = _first_func(spec, min_funcs=3)
+    spec.arrays["func_threshold"][f0] = spec.arrays["func_threshold"][f0 + 1] + 1
+
+
+def _input_range(spec):
+    _, f0 = _first_func(spec, min_arity=1)
+    spec.arrays["func_inputs"][4 * f0] = spec.n + int(spec.arrays["n_gates"][0])
+
+
+def _table_bits(spec):
+    spec.arrays["func_table"][0] |= 1 << 16
+
+
+def _null_attractors(spec):
+    spec.desc.attractor_start = None
+
+
+def _attractor_start(spec):
+    spec.arrays["attractor_start"][0] = 1
+
+
+def _empty_attractor(spec):
+    assert len(spec.attractors) >= 2
+    spec.arrays["attractor_start"][1] = 0
+
+
+def _cdf_decreases(spec):
+    spec.arrays["perturb_cdf"][1] = 0
+
+
+def _too_many_gates(spec):
+    spec.desc.n_gates = 300
+
+
+def _negative_gates(spec):
+    spec.desc.n_gates = -1
+
+
+N_GATES_MSG = "n_gates out of range (32 * W + n_gates must be <= 256)"
+
+
+@pytest.mark.parametrize("network,mutate,msg", [
+    ("bb33", _gate_arity, "gate arity must be 0..4"),
+    ("bb33", _gate_table_bits, "gate truth table has bits beyond 2^arity"),
+    ("bb33", _gate_input_order, "gate input must be a node or an earlier gate"),
+    ("pbn7", _func_start_span, "node_func_start must span 0..n_funcs"),
+    ("pbn7", _func_count, "node 0 needs 1..16 functions"),
+    ("pbn7", _func_arity, "function arity must be 0..4"),
+    ("pbn7", _thresholds_decrease, "thresholds must be non-decreasing and <= 2^prob_bits"),
+    ("bb33", _input_range, "function input reference out of range"),
+    ("pbn7", _table_bits, "truth table has bits beyond 2^arity"),
+    ("pbn7", _null_attractors, "null attractor tables"),
+    ("pbn7", _attractor_start, "bad attractor_start"),
+    ("pbn28", _empty_attractor, "empty attractor"),
+    ("pbn7", _cdf_decreases, "perturb_cdf must be non-decreasing"),
+    ("pbn7", _too_many_gates, N_GATES_MSG),
+    ("pbn7", _negative_gates, N_GATES_MSG),
+], ids=lambda v: getattr(v, "__name__", None))
+def test_create_rejects_with_the_reason(lib, network, mutate, msg):
+    """Every rejection of the descriptor compiler through the real library (all of them come
+    before the first device call), with the message pbn_last_error reports."""
+    spec = EnvSpec(load_network(network), load_attractors(network))
+    mutate(spec)
+    rc, err = _create(lib, spec)
+    assert rc == -22 and err == msg
+
+
 def test_step_rejects_null_net(lib):
     rc = lib.pbn_step(None, 0, 0, 0, 32, 3, None, None, None, None, None, None, None, None, None)
     assert rc == -22
