@@ -697,6 +697,72 @@ int pbn_per_update(int32_t batch, int64_t capacity, int64_t tree_size, double al
                    const int64_t* d_idx, const float* d_priorities, double* d_max_priority, double* d_sum_tree,
                    double* d_min_tree, void* stream);
 
+/*
+ * The DDQN / DDQNPER agent (ddqn_per/__init__.py, ddqn_per/network.py; pbn_rl_amd/ddqn.py,
+ * csrc/pbn_ddqn.hip).  Additive exports (the ABI version is unchanged).  The network is the
+ * reference's DQN with one hidden Linear (network.py:24-28): input = nn.Bilinear(N, N, h0), ReLU,
+ * linears.0 = Linear(h0, h1), ReLU, output = Linear(h1, N + 1); h0, h1 in 1..64, N + 1 <= 128.
+ * None of these allocates or synchronises; every counter is read from device memory when the
+ * kernels run, so every launch can be captured in a graph.
+ *
+ * pbn_dqn_layout: the float offsets of the flat parameter buffer's six segments, each 16-float
+ *   aligned, then its size (offsets[7]): input.weight (h0, N, N), input.bias, linears.0.weight
+ *   (h1, h0), linears.0.bias, output.weight (N + 1, h1), output.bias.  Parameters, Adam's moments
+ *   and the gradient share it.
+ * pbn_dqn_image_floats / pbn_dqn_pack: the network's image, what the acting and update kernels
+ *   read (H0p, H1p, Ap: h0, h1, N + 1 rounded up to multiples of 16; padding is zero):
+ *     T   [n_attr][N][H0p]  T[t][i][o] = sum_j x_t[j] W[o][i][j], x_t attractor t's first state, j
+ *                           ascending: DQN.forward's first layer (network.py:40) is
+ *                           bias + sum_{i: s_i = 1} T[target][i][:]; target id 255 reads no row
+ *     the three biases, padded; then 16 x 16 tiles in v_mfma_f32_16x16x4_f32 fragment order:
+ *     linears.0.weight (lane 16g + r of tile (ot, kt) holds W[16 ot + r][16 kt + 4g + v]), the
+ *     same for the backward's transposed product (W[16 ot + 4g + v][16 kt + r]), output.weight.
+ *   d_params and d_image 16-byte aligned.
+ * pbn_dqn_flipmask_from_state: DDQN.predict (ddqn_per/__init__.py:155-179) for n_envs envs (any
+ *   multiple of 32) in one launch: packed state uint32 [W][n] + target id uint8 [n] + image -> Q
+ *   (d_q float [n][N + 1], nullable) -> epsilon-greedy -> d_actions int32 [n] (nullable) and
+ *   d_flipmask uint32 [W][n] (action 0 is the no-op, :351; action a > 0 flips node a - 1).  The
+ *   EXPLORE law of pbn_q_to_flipmask with one branch: explore iff EXPLORE word 0 of (seed, env_offset
+ *   + env, step) < floor(epsilon * 2^32), then a = (word 1 * (N + 1)) >> 32; else the first maximum
+ *   of Q.  d_step / d_epsilon, when not null, replace step / epsilon and are read by the kernel.
+ * pbn_ddqn_learn_workspace / pbn_ddqn_learn: DDQN._learn_step (:275-278: _get_loss :218-256,
+ *   _back_propagate :258-267) or, with d_weights and d_priority, DDQNPER._learn_step (:468-483) on
+ *   rows d_idx[B] of the replay ring (pbn_replay_store's layout, n_branches = 1; B a multiple of 16
+ *   in 16..1024).  In fp32, g_b the row's target attractor's first state:
+ *     q_b = Q(s_b, g_b)[a_b];  a'_b = argmax_a Q(s'_b, g_b) (first maximum)
+ *     y_b = r_b + (1 - done_b) gamma Q_target(s'_b, g_b)[a'_b];  delta_b = q_b - y_b
+ *     h_b = 0.5 delta_b^2 if |delta_b| < 1 else |delta_b| - 0.5
+ *     l_b = w_b h_b (h_b without weights);  loss = (sum_b l_b, b ascending) / B
+ *     d_priority[b] = |l_b| + replay_constant, by batch position
+ *     dloss/dq_b = (clamp(delta_b, -1, 1) / B) * w_b: unit weights give the unweighted update's
+ *     gradient, Adam step and image bit for bit
+ *   then clip_grad_norm_ (total = the L2 norm of the whole gradient, coef = min(1, max_grad_norm /
+ *   (total + 1e-6)), every gradient times coef), torch.optim.Adam's step on d_params / d_adam_m /
+ *   d_adam_v (layout as d_params; *d_adam_step, a float, is incremented), and the new online image
+ *   (bit-equal to pbn_dqn_pack of the new weights).  The target network enters through its image
+ *   alone.  Outputs: d_loss[1], d_grad_norm[1] (total, before clipping) and, when d_grad is not null,
+ *   the clipped gradient in the layout.  Four launches (forward + TD + backward; gradient tiles and
+ *   per-block sums of squares; norm + clip + Adam; image); every sum runs in a fixed order, so two
+ *   runs from the same state give the same bits.  Rejects shapes outside the above, a null or
+ *   misaligned buffer (parameters, moments, images, workspace, d_grad: 16-byte), one of d_weights /
+ *   d_priority without the other, and a workspace smaller than pbn_ddqn_learn_workspace's.
+ */
+int pbn_dqn_layout(int32_t n_nodes, int32_t h0, int32_t h1, int64_t* offsets);
+int pbn_dqn_image_floats(const pbn_net* net, int32_t h0, int32_t h1, int64_t* n_floats);
+int pbn_dqn_pack(const pbn_net* net, int32_t h0, int32_t h1, const float* d_params, float* d_image, void* stream);
+int pbn_dqn_flipmask_from_state(const pbn_net* net, uint64_t seed, uint64_t step, const uint64_t* d_step,
+                                uint64_t env_offset, int64_t n_envs, const uint32_t* d_state, const uint8_t* d_target,
+                                int32_t h0, int32_t h1, const float* d_image, float epsilon, const float* d_epsilon,
+                                float* d_q, uint32_t* d_flipmask, int32_t* d_actions, void* stream);
+int pbn_ddqn_learn_workspace(int32_t n_nodes, int32_t h0, int32_t h1, int64_t batch, int64_t* bytes);
+int pbn_ddqn_learn(const pbn_net* net, int32_t h0, int32_t h1, int64_t batch, const int64_t* d_idx, int64_t capacity,
+                   const uint32_t* d_state, const uint32_t* d_next_state, const uint8_t* d_target,
+                   const int32_t* d_action, const float* d_reward, const uint8_t* d_done, float* d_params,
+                   float* d_image, const float* d_target_image, float* d_adam_m, float* d_adam_v, float* d_adam_step,
+                   float lr, float beta1, float beta2, float eps, float gamma, float max_grad_norm, void* d_workspace,
+                   int64_t workspace_bytes, float* d_loss, float* d_grad_norm, float* d_grad, const float* d_weights,
+                   float replay_constant, float* d_priority, void* stream);
+
 const char* pbn_last_error(void);
 int pbn_abi_version(void);
 

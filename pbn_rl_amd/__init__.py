@@ -7,5 +7,6 @@ Public surface:
   vector_env.VectorPBNEnv            batched envs in HBM, stepped by libpbn_env.so
   env.PBNEnv / make                  scalar gym-style facade (drop-in under train_BDQ.py)
   evaluate.evaluate_control          source -> target control evaluation of a trained agent
+  ddqn.DQN / DDQNLearner             the reference's DDQN / DDQN-PER agent over the batched envs
 """
 __version__ = "0.1.0"

@@ -31,9 +31,11 @@ EXPORTS = ["pbn_net_create", "pbn_net_destroy", "pbn_net_words", "pbn_reset", "p
            "pbn_qnet_flipmask_from_state", "pbn_replay_store", "pbn_replay_advance", "pbn_replay_batch", "pbn_bdq_td_loss", "pbn_bdq_layout", "pbn_bdq_learn_workspace",
            "pbn_bdq_pack", "pbn_bdq_image_floats", "pbn_bdq_learn", "pbn_copy_async", "pbn_rollout_copy", "pbn_host_buffer", "pbn_host_buffer_free", "pbn_stream_sync",
            "pbn_eval_track", "pbn_eval_reduce", "pbn_per_store", "pbn_per_sample", "pbn_per_update",
-           "pbn_bdq_td_loss_per", "pbn_bdq_learn_per", "pbn_last_error", "pbn_abi_version"]
+           "pbn_bdq_td_loss_per", "pbn_bdq_learn_per", "pbn_dqn_layout", "pbn_dqn_image_floats", "pbn_dqn_pack",
+           "pbn_dqn_flipmask_from_state", "pbn_ddqn_learn_workspace", "pbn_ddqn_learn", "pbn_last_error",
+           "pbn_abi_version"]
 SOURCES = ["pbn_env.hip", "pbn_settle.hip", "pbn_agent.hip", "pbn_qnet.hip", "pbn_learn.hip", "pbn_eval.hip",
-           "pbn_per.hip"]
+           "pbn_per.hip", "pbn_ddqn.hip"]
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -204,6 +206,21 @@ def load() -> ctypes.CDLL:
         L.pbn_bdq_learn_per.argtypes = ([vp, i64, vp, i64, vp, vp, vp, vp, i32, vp, vp] + [vp] * 7 + [f32] * 7 +
                                         [vp, i64, vp, vp, vp, f32, vp, vp, vp])
         L.pbn_bdq_learn_per.restype = ctypes.c_int
+    if hasattr(L, "pbn_ddqn_learn"):   # (additive exports of ABI 11: the DDQN / DDQNPER agent)
+        L.pbn_dqn_layout.argtypes = [i32, i32, i32, vp]
+        L.pbn_dqn_layout.restype = ctypes.c_int
+        L.pbn_dqn_image_floats.argtypes = [vp, i32, i32, vp]
+        L.pbn_dqn_image_floats.restype = ctypes.c_int
+        L.pbn_dqn_pack.argtypes = [vp, i32, i32, vp, vp, vp]
+        L.pbn_dqn_pack.restype = ctypes.c_int
+        L.pbn_dqn_flipmask_from_state.argtypes = [vp, u64, u64, vp, u64, i64, vp, vp, i32, i32, vp, f32, vp, vp, vp,
+                                                  vp, vp]
+        L.pbn_dqn_flipmask_from_state.restype = ctypes.c_int
+        L.pbn_ddqn_learn_workspace.argtypes = [i32, i32, i32, i64, vp]
+        L.pbn_ddqn_learn_workspace.restype = ctypes.c_int
+        L.pbn_ddqn_learn.argtypes = ([vp, i32, i32, i64, vp, i64] + [vp] * 6 + [vp] * 6 + [f32] * 6 +
+                                     [vp, i64, vp, vp, vp, vp, f32, vp, vp])
+        L.pbn_ddqn_learn.restype = ctypes.c_int
     L.pbn_abi_version.argtypes = []
     L.pbn_abi_version.restype = ctypes.c_int
     _lib = L

@@ -1,0 +1,848 @@
+// pbn_ddqn.hip -- the reference's other agent, DDQN / DDQNPER (ddqn_per/__init__.py, driven by
+// train_ddqn.py), on the device: batched acting for a whole VectorPBNEnv in one launch and
+// _learn_step (:275-278, :468-483) as four launches over one flat parameter buffer.
+//
+// The network is ddqn_per/network.py's DQN with one hidden Linear: an nn.Bilinear(N, N, h0) input
+// layer on (state, target), ReLU, Linear(h0, h1), ReLU, Linear(h1, N + 1).  As in pbn_learn.hip the
+// bilinear layer is never evaluated as such: the target half of the input is one of the net's
+// attractors' first states, so the layer contracted with each of them is a table
+// T[t][i][o] = sum_j x_t[j] W[o][i][j], and a row's first layer is bias + the table rows of its
+// state's set bits.  The two dense layers run on v_mfma_f32_16x16x4_f32 with 16 rows (envs or
+// transitions) as the MFMA's columns: a lane's accumulator of output tile ot, D[16 ot + 4g + v][r],
+// is exactly the B operand of the next layer's k-block ot, so the activations never leave the
+// registers.
+//
+//   dqn_pack     the network image of a flat parameter buffer (below).
+//   dqn_act      one wave per 16 envs: packed state + target id -> Q -> epsilon-greedy under the
+//                EXPLORE law (pbn_q_to_flipmask's, one branch) -> action and flip-mask words.
+//   ddqn_fb      B/16 blocks of three waves: the online network on s, the online network on s'
+//                (its first argmax), the target network on s'; then wave 0 takes the TD error, the
+//                Huber loss and its gradient and runs the backward, storing the activations and
+//                deltas as [feature][B] planes.
+//   ddqn_grad    the weight gradients in the parameter layout (the bilinear one from the packed
+//                state and target bits, the dense ones as 16 x 16 MFMA tiles with K = the batch) and
+//                one sum of squares per block.
+//   ddqn_adam    every block adds the blocks' sums in the same fixed order (the total norm of
+//                clip_grad_norm_), scales the gradient and takes the Adam step.
+//   dqn_pack     again, on the new weights: the online image.
+//
+// Every reduction runs in a fixed order and nothing is accumulated with atomics: two runs from the
+// same state give the same bits.
+#include <hip/hip_runtime.h>
+
+#include <limits.h>
+#include <math.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "../../include/pbn_env.h"
+#include "net_view.h"
+#include "philox.h"
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kMaxHT = 4;       // hidden widths <= 64: at most four 16-wide tiles
+constexpr int kMaxA = 128;      // N + 1 <= 128
+constexpr int kActWaves = 4;
+constexpr int kGradThreads = 256;
+
+enum Seg { BIL_W, BIL_B, L1_W, L1_B, OUT_W, OUT_B, TOTAL };
+
+inline int64_t al16(int64_t x) { return (x + 15) & ~int64_t(15); }
+
+// Shapes, the parameter layout (pbn_dqn_layout) and the image layout.  Image (floats):
+//   T     [n_attr][N][H0p]   the bilinear layer contracted with each attractor's first state,
+//                            zero past h0 (a row without a target reads none of it)
+//   b0 [H0p], b1 [H1p], b2 [Ap]   the biases, zero-padded
+//   w1f   [H1p/16][H0p/16][64][4]  linears.0: lane 16g + r holds W[16 ot + r][16 kt + 4g + v]
+//   w1b   [H1p/16][H0p/16][64][4]  its transpose's operand: W[16 ot + 4g + v][16 kt + r]
+//   w2f   [Ap/16][H1p/16][64][4]   output, as w1f
+struct Dims {
+  int N, W, n_attr, h0, h1, A, H0p, H1p, Ap, H0T, H1T, AT;
+  int64_t off[TOTAL + 1], sz[TOTAL];
+  int64_t iT, ib0, ib1, ib2, iw1f, iw1b, iw2f, itotal;
+};
+
+const char* shape_error(int N, int h0, int h1) {
+  if (N < 1 || N + 1 > kMaxA) return "n_nodes must be 1..127 (N + 1 <= 128 actions)";
+  if (h0 < 1 || h0 > 64 || h1 < 1 || h1 > 64) return "hidden widths must be 1..64";
+  return nullptr;
+}
+
+void make_dims(int N, int W, int n_attr, int h0, int h1, Dims* d) {
+  d->N = N;
+  d->W = W;
+  d->n_attr = n_attr;
+  d->h0 = h0;
+  d->h1 = h1;
+  d->A = N + 1;
+  d->H0T = (h0 + 15) / 16;
+  d->H1T = (h1 + 15) / 16;
+  d->AT = (N + 1 + 15) / 16;
+  d->H0p = 16 * d->H0T;
+  d->H1p = 16 * d->H1T;
+  d->Ap = 16 * d->AT;
+  const int64_t sz[TOTAL] = {(int64_t)h0 * N * N, h0, (int64_t)h1 * h0, h1, (int64_t)d->A * h1, d->A};
+  int64_t o = 0;
+  for (int s = 0; s < TOTAL; ++s) {
+    d->sz[s] = sz[s];
+    d->off[s] = o;
+    o += al16(sz[s]);
+  }
+  d->off[TOTAL] = o;
+  int64_t i = 0;
+  d->iT = i;
+  i += (int64_t)n_attr * N * d->H0p;
+  d->ib0 = i;
+  i += d->H0p;
+  d->ib1 = i;
+  i += d->H1p;
+  d->ib2 = i;
+  i += d->Ap;
+  d->iw1f = i;
+  i += (int64_t)d->H1p * d->H0p;
+  d->iw1b = i;
+  i += (int64_t)d->H1p * d->H0p;
+  d->iw2f = i;
+  i += (int64_t)d->Ap * d->H1p;
+  d->itotal = i;
+}
+
+__device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
+
+// ---- the image -------------------------------------------------------------------------------
+// Element e of the image of parameters P.  A table entry adds its weights by ascending j.
+__device__ float image_value(const Dims& d, const float* __restrict__ P, const uint32_t* __restrict__ att_first,
+                             int64_t e) {
+  if (e < d.ib0) {
+    const int o = (int)(e % d.H0p);
+    const int64_t ti = e / d.H0p;
+    const int i = (int)(ti % d.N), t = (int)(ti / d.N);
+    if (o >= d.h0) return 0.f;
+    const float* w = P + d.off[BIL_W] + ((int64_t)o * d.N + i) * d.N;
+    float s = 0.f;
+    for (int j = 0; j < d.N; ++j)
+      if ((att_first[(size_t)t * d.W + (j >> 5)] >> (j & 31)) & 1u) s += w[j];
+    return s;
+  }
+  if (e < d.ib1) return e - d.ib0 < d.h0 ? P[d.off[BIL_B] + e - d.ib0] : 0.f;
+  if (e < d.ib2) return e - d.ib1 < d.h1 ? P[d.off[L1_B] + e - d.ib1] : 0.f;
+  if (e < d.iw1f) return e - d.ib2 < d.A ? P[d.off[OUT_B] + e - d.ib2] : 0.f;
+  const bool second = e >= d.iw2f, bwd = !second && e >= d.iw1b;
+  const int64_t x = e - (second ? d.iw2f : (bwd ? d.iw1b : d.iw1f));
+  const int KT = second ? d.H1T : d.H0T;
+  const int tile = (int)(x >> 8), lane = (int)(x >> 2) & 63, v = (int)x & 3;
+  const int ot = tile / KT, kt = tile - ot * KT, g = lane >> 4, r = lane & 15;
+  const int row = bwd ? 16 * ot + 4 * g + v : 16 * ot + r;
+  const int col = bwd ? 16 * kt + r : 16 * kt + 4 * g + v;
+  const int rows = second ? d.A : d.h1, cols = second ? d.h1 : d.h0;
+  if (row >= rows || col >= cols) return 0.f;
+  return P[d.off[second ? OUT_W : L1_W] + (int64_t)row * cols + col];
+}
+
+__global__ void __launch_bounds__(256) dqn_pack_kernel(Dims d, const float* __restrict__ P,
+                                                        const uint32_t* __restrict__ att_first, float* __restrict__ img) {
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < d.itotal; e += (int64_t)gridDim.x * 256)
+    img[e] = image_value(d, P, att_first, e);
+}
+
+// ---- the forward of 16 rows on one wave --------------------------------------------------------
+// Lane 16g + r works on row r.  sw: the row's state words (bits past N cleared), t: its target id.
+// y0[kb] / y1[kb] hold features 16 kb + 4g + v of row r after the ReLU (zero in the padding);
+// qf(at, q) receives Q[16 at + 4g + v][r] tile by tile, at ascending.
+template <class QF>
+__device__ __forceinline__ void forward16(const Dims& d, const float* __restrict__ img, const uint32_t (&sw)[4], int t,
+                                          int lane, float4 (&y0)[kMaxHT], float4 (&y1)[kMaxHT], QF&& qf) {
+  const int g = lane >> 4;
+  // bilinear layer: bias + the table rows of the set bits, i ascending
+#pragma unroll
+  for (int kb = 0; kb < kMaxHT; ++kb)
+    y0[kb] = kb < d.H0T ? *reinterpret_cast<const float4*>(img + d.ib0 + 16 * kb + 4 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
+  if (t < d.n_attr) {
+    const float* T = img + d.iT + (int64_t)t * d.N * d.H0p + 4 * g;
+    // four set bits a round: their table rows are requested together (one round trip, not four)
+    // and added in order; a slot past the last bit reads row 0 and adds zeros
+    for (int w = 0; w < d.W; ++w) {
+      uint32_t x = sw[w];
+      while (x) {
+        float4 tv[4][kMaxHT];
+        bool on[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          on[u] = x != 0u;
+          const int i = on[u] ? 32 * w + __builtin_ctz(x) : 0;
+          x &= x - 1u;
+          const float* row = T + (int64_t)i * d.H0p;
+#pragma unroll
+          for (int kb = 0; kb < kMaxHT; ++kb)
+            if (kb < d.H0T) tv[u][kb] = *reinterpret_cast<const float4*>(row + 16 * kb);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+          for (int kb = 0; kb < kMaxHT; ++kb)
+            if (kb < d.H0T) {
+              y0[kb].x += on[u] ? tv[u][kb].x : 0.f;
+              y0[kb].y += on[u] ? tv[u][kb].y : 0.f;
+              y0[kb].z += on[u] ? tv[u][kb].z : 0.f;
+              y0[kb].w += on[u] ? tv[u][kb].w : 0.f;
+            }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int kb = 0; kb < kMaxHT; ++kb) {
+    y0[kb].x = fmaxf(y0[kb].x, 0.f);
+    y0[kb].y = fmaxf(y0[kb].y, 0.f);
+    y0[kb].z = fmaxf(y0[kb].z, 0.f);
+    y0[kb].w = fmaxf(y0[kb].w, 0.f);
+  }
+  // linears.0
+  const float4* w1 = reinterpret_cast<const float4*>(img + d.iw1f) + lane;
+#pragma unroll
+  for (int ot = 0; ot < kMaxHT; ++ot) {
+    y1[ot] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (ot < d.H1T) {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int kb = 0; kb < kMaxHT; ++kb)
+        if (kb < d.H0T) {
+          const float4 w = w1[(ot * d.H0T + kb) * 64];
+          acc = mfma(w.x, y0[kb].x, acc);
+          acc = mfma(w.y, y0[kb].y, acc);
+          acc = mfma(w.z, y0[kb].z, acc);
+          acc = mfma(w.w, y0[kb].w, acc);
+        }
+      const float4 b = *reinterpret_cast<const float4*>(img + d.ib1 + 16 * ot + 4 * g);
+      y1[ot] = make_float4(fmaxf(acc[0] + b.x, 0.f), fmaxf(acc[1] + b.y, 0.f), fmaxf(acc[2] + b.z, 0.f),
+                           fmaxf(acc[3] + b.w, 0.f));
+    }
+  }
+  // output
+  const float4* w2 = reinterpret_cast<const float4*>(img + d.iw2f) + lane;
+  for (int at = 0; at < d.AT; ++at) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kb = 0; kb < kMaxHT; ++kb)
+      if (kb < d.H1T) {
+        const float4 w = w2[(at * d.H1T + kb) * 64];
+        acc = mfma(w.x, y1[kb].x, acc);
+        acc = mfma(w.y, y1[kb].y, acc);
+        acc = mfma(w.z, y1[kb].z, acc);
+        acc = mfma(w.w, y1[kb].w, acc);
+      }
+    const float4 b = *reinterpret_cast<const float4*>(img + d.ib2 + 16 * at + 4 * g);
+    const f32x4 q = {acc[0] + b.x, acc[1] + b.y, acc[2] + b.z, acc[3] + b.w};
+    qf(at, q);
+  }
+}
+
+// torch.argmax's order: NaN is the maximum, of equals the lower index wins
+__device__ __forceinline__ bool better(float a, int ia, float b, int ib) {
+  if (isnan(a)) return isnan(b) ? ia < ib : true;
+  if (isnan(b)) return false;
+  return a > b || (a == b && ia < ib);
+}
+
+// the first maximum of a row whose lanes (g = 0..3) each hold a running (best, index)
+__device__ __forceinline__ int row_argmax(float best, int bi) {
+#pragma unroll
+  for (int m = 16; m <= 32; m <<= 1) {
+    const float ob = __shfl_xor(best, m);
+    const int oi = __shfl_xor(bi, m);
+    if (better(ob, oi, best, bi)) {
+      best = ob;
+      bi = oi;
+    }
+  }
+  return bi;
+}
+
+__device__ __forceinline__ void load_words(const Dims& d, const uint32_t* __restrict__ st, int64_t stride, int64_t j,
+                                           uint32_t (&sw)[4]) {
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    uint32_t x = w < d.W ? st[(size_t)w * stride + j] : 0u;
+    if (w == d.W - 1 && (d.N & 31)) x &= (1u << (d.N & 31)) - 1u;
+    sw[w] = x;
+  }
+}
+
+// ---- acting ------------------------------------------------------------------------------------
+struct ActArgs {
+  Dims d;
+  int64_t n;
+  const uint32_t* state;
+  const uint8_t* target;
+  const float* img;
+  uint64_t seed, step, env_offset, eps_u;
+  const uint64_t* d_step;
+  const float* d_eps;
+  float* q;
+  uint32_t* flipmask;
+  int32_t* actions;
+};
+
+__global__ void __launch_bounds__(64 * kActWaves) dqn_act_kernel(ActArgs a) {
+  const Dims& d = a.d;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t tile = (int64_t)blockIdx.x * kActWaves + wave;
+  if (tile >= a.n / 16) return;   // (wave-uniform; the kernel has no block barrier)
+  const int g = lane >> 4, r = lane & 15;
+  const int64_t e = tile * 16 + r;
+  uint32_t sw[4];
+  load_words(d, a.state, a.n, e, sw);
+  const int t = a.target[e];
+  float4 y0[kMaxHT], y1[kMaxHT];
+  float best = -INFINITY;
+  int bi = INT_MAX;
+  forward16(d, a.img, sw, t, lane, y0, y1, [&](int at, f32x4 q) {
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int ai = 16 * at + 4 * g + v;
+      if (ai < d.A) {
+        if (a.q) a.q[(size_t)e * d.A + ai] = q[v];
+        if (better(q[v], ai, best, bi)) {
+          best = q[v];
+          bi = ai;
+        }
+      }
+    }
+  });
+  bi = row_argmax(best, bi);
+  if (g != 0) return;
+  // EXPLORE law (DESIGN.md "Step semantics" 6), one branch: explore iff word 0 < floor(eps 2^32),
+  // then word 1 by multiply-high onto [0, N]
+  const uint64_t st = a.d_step ? *a.d_step : a.step;
+  const pbn::Word4 rw = pbn::draw(a.seed, a.env_offset + (uint64_t)e, st, pbn::kStreamExplore, 0);
+  uint64_t eps_u = a.eps_u;
+  if (a.d_eps) {   // device epsilon: clamped to [0, 1], NaN -> 0
+    const float ef = fminf(fmaxf(*a.d_eps, 0.f), 1.f);
+    eps_u = (uint64_t)floor((double)ef * 4294967296.0);
+  }
+  const int act = (uint64_t)rw.x < eps_u ? (int)__umulhi(rw.y, (uint32_t)d.A) : bi;
+  if (a.actions) a.actions[e] = act;
+#pragma unroll
+  for (int w = 0; w < 4; ++w)
+    if (w < d.W) a.flipmask[(size_t)w * a.n + e] = (act > 0 && act <= d.N && ((act - 1) >> 5) == w) ? 1u << ((act - 1) & 31) : 0u;
+}
+
+// ---- the update --------------------------------------------------------------------------------
+struct Work {   // float offsets into the workspace
+  int64_t y0, y1, dz0, dz1, gq, lrow, act, srow, trow, partial, G, total;
+  int nb_bil, nb_w1, nb_w2, nblocks;
+};
+
+Work make_work(const Dims& d, int64_t B) {
+  Work w;
+  int64_t o = 0;
+  auto take = [&](int64_t n) {
+    const int64_t at = o;
+    o += al16(n);
+    return at;
+  };
+  w.y0 = take(d.H0p * B);
+  w.y1 = take(d.H1p * B);
+  w.dz0 = take(d.H0p * B);
+  w.dz1 = take(d.H1p * B);
+  w.gq = take(B);
+  w.lrow = take(B);
+  w.act = take(B);
+  w.srow = take(4 * B);
+  w.trow = take(4 * B);
+  w.nb_bil = (int)((d.sz[BIL_W] + kGradThreads - 1) / kGradThreads);
+  w.nb_w1 = (d.H1T * d.H0T + 3) / 4;
+  w.nb_w2 = (d.AT * d.H1T + 3) / 4;
+  w.nblocks = w.nb_bil + 1 + w.nb_w1 + w.nb_w2;
+  w.partial = take(w.nblocks);
+  w.G = take(d.off[TOTAL]);
+  w.total = o;
+  return w;
+}
+
+struct LearnArgs {
+  Dims d;
+  Work w;
+  int B;
+  const int64_t* idx;
+  int64_t cap;
+  const uint32_t* st;
+  const uint32_t* nst;
+  const uint8_t* tgt;
+  const int32_t* act;
+  const float* rew;
+  const uint8_t* done;
+  const uint32_t* att_first;
+  float* P;
+  const float* img;
+  const float* timg;
+  float* m;
+  float* v;
+  float* step;
+  float lr, b1, b2, eps, gamma, max_norm, rconst;
+  float* ws;
+  float* loss;
+  float* grad_norm;
+  float* grad;
+  const float* wts;
+  float* prio;
+};
+
+__global__ void __launch_bounds__(192) ddqn_fb_kernel(LearnArgs a) {
+  __shared__ int s_ap[16];
+  __shared__ float s_qt[kMaxA * 16];
+  const Dims& d = a.d;
+  const int B = a.B;
+  const int lane = threadIdx.x & 63, set = threadIdx.x >> 6;   // 0: Q(s), 1: Q(s'), 2: Q_target(s')
+  const int g = lane >> 4, r = lane & 15;
+  const int b = blockIdx.x * 16 + r;
+  int64_t j = a.idx[b];
+  j = j < 0 ? 0 : (j >= a.cap ? a.cap - 1 : j);
+  uint32_t sw[4];
+  load_words(d, set == 0 ? a.st : a.nst, a.cap, j, sw);
+  const int t = a.tgt[j];
+  const int act = min(max(a.act[j], 0), d.A - 1);
+  float4 y0[kMaxHT], y1[kMaxHT];
+  float best = -INFINITY, qsel = 0.f;
+  int bi = INT_MAX;
+  forward16(d, set == 2 ? a.timg : a.img, sw, t, lane, y0, y1, [&](int at, f32x4 q) {
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int ai = 16 * at + 4 * g + v;
+      if (ai < d.A) {
+        if (set == 0 && ai == act) qsel = q[v];
+        if (set == 1 && better(q[v], ai, best, bi)) {
+          best = q[v];
+          bi = ai;
+        }
+        if (set == 2) s_qt[ai * 16 + r] = q[v];
+      }
+    }
+  });
+  if (set == 1) {
+    bi = row_argmax(best, bi);
+    if (g == 0) s_ap[r] = min(bi, d.A - 1);
+  }
+  __syncthreads();
+  if (set != 0) return;
+  // Q(s)[a]: one lane of the row's four holds it, the others add zeros
+  qsel += __shfl_xor(qsel, 16);
+  qsel += __shfl_xor(qsel, 32);
+  const float qt = s_qt[s_ap[r] * 16 + r];
+  const float y = a.rew[j] + ((1.f - (a.done[j] ? 1.f : 0.f)) * a.gamma) * qt;
+  const float delta = qsel - y, ad = fabsf(delta);
+  const float h = ad < 1.f ? 0.5f * delta * delta : ad - 0.5f;
+  float gq = fminf(fmaxf(delta, -1.f), 1.f) * (1.f / (float)B);   // d mean_b h_b / d q_b
+  float l = h;
+  if (a.wts) {
+    const float wb = a.wts[b];
+    gq *= wb;
+    l = h * wb;
+    if (g == 0) a.prio[b] = fabsf(l) + a.rconst;
+  }
+  float* ws = a.ws;
+  if (g == 0) {
+    ws[a.w.gq + b] = gq;
+    ws[a.w.lrow + b] = l;
+    reinterpret_cast<int*>(ws + a.w.act)[b] = act;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      reinterpret_cast<uint32_t*>(ws + a.w.srow)[w * B + b] = sw[w];
+      reinterpret_cast<uint32_t*>(ws + a.w.trow)[w * B + b] =
+          (t < d.n_attr && w < d.W) ? a.att_first[(size_t)t * d.W + w] : 0u;
+    }
+    if (blockIdx.x == 0 && r == 0) a.step[0] += 1.f;   // Adam's step count, read by ddqn_adam
+  }
+  // backward.  dQ is gq at (a_b, b) alone, so the output layer's transpose is one weight row
+  float4 dz1[kMaxHT], dz0[kMaxHT];
+  const float* wo = a.P + d.off[OUT_W] + (int64_t)act * d.h1;
+#pragma unroll
+  for (int kb = 0; kb < kMaxHT; ++kb) {
+    float dv[4];
+    const float* yv = &y1[kb].x;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int k = 16 * kb + 4 * g + v;
+      dv[v] = (kb < d.H1T && k < d.h1 && yv[v] > 0.f) ? wo[k] * gq : 0.f;
+    }
+    dz1[kb] = make_float4(dv[0], dv[1], dv[2], dv[3]);
+  }
+  const float4* w1b = reinterpret_cast<const float4*>(a.img + d.iw1b) + lane;
+#pragma unroll
+  for (int kt = 0; kt < kMaxHT; ++kt) {
+    dz0[kt] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (kt < d.H0T) {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ot = 0; ot < kMaxHT; ++ot)
+        if (ot < d.H1T) {
+          const float4 w = w1b[(ot * d.H0T + kt) * 64];
+          acc = mfma(w.x, dz1[ot].x, acc);
+          acc = mfma(w.y, dz1[ot].y, acc);
+          acc = mfma(w.z, dz1[ot].z, acc);
+          acc = mfma(w.w, dz1[ot].w, acc);
+        }
+      dz0[kt] = make_float4(y0[kt].x > 0.f ? acc[0] : 0.f, y0[kt].y > 0.f ? acc[1] : 0.f,
+                            y0[kt].z > 0.f ? acc[2] : 0.f, y0[kt].w > 0.f ? acc[3] : 0.f);
+    }
+  }
+#pragma unroll
+  for (int kb = 0; kb < kMaxHT; ++kb) {
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int k = 16 * kb + 4 * g + v;
+      if (kb < d.H0T) {
+        ws[a.w.y0 + (int64_t)k * B + b] = (&y0[kb].x)[v];
+        ws[a.w.dz0 + (int64_t)k * B + b] = (&dz0[kb].x)[v];
+      }
+      if (kb < d.H1T) {
+        ws[a.w.y1 + (int64_t)k * B + b] = (&y1[kb].x)[v];
+        ws[a.w.dz1 + (int64_t)k * B + b] = (&dz1[kb].x)[v];
+      }
+    }
+  }
+}
+
+// dW[16 ot + 4g + v][16 kt + (lane & 15)] = sum_b X[16 ot + ..][b] Y[16 kt + ..][b], b ascending in
+// blocks of 16; xa(o, b4) gives X[16 ot + o][b4 .. b4 + 3]
+template <class XA>
+__device__ __forceinline__ f32x4 grad_tile(const float* __restrict__ Y, int kt, int B, int lane, XA&& xa) {
+  const int g = lane >> 4, c = lane & 15;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  for (int b0 = 0; b0 < B; b0 += 16) {
+    const float4 x = xa(c, b0 + 4 * g);
+    const float4 y = *reinterpret_cast<const float4*>(Y + (int64_t)(16 * kt + c) * B + b0 + 4 * g);
+    acc = mfma(x.x, y.x, acc);
+    acc = mfma(x.y, y.y, acc);
+    acc = mfma(x.z, y.z, acc);
+    acc = mfma(x.w, y.w, acc);
+  }
+  return acc;
+}
+
+__global__ void __launch_bounds__(kGradThreads) ddqn_grad_kernel(LearnArgs a) {
+  __shared__ float red[kGradThreads];
+  const Dims& d = a.d;
+  const Work& w = a.w;
+  const int B = a.B, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* ws = a.ws;
+  float* G = a.ws + w.G;
+  const float* gq = ws + w.gq;
+  const int* act = reinterpret_cast<const int*>(ws + w.act);
+  float ss = 0.f;
+  int blk = blockIdx.x;
+  if (blk < w.nb_bil) {
+    // dW[o][i][j] = sum_b dz0[o][b] s_i[b] x_j[b], b ascending
+    const int64_t e = (int64_t)blk * kGradThreads + tid;
+    if (e < d.sz[BIL_W]) {
+      const int jn = (int)(e % d.N), i = (int)((e / d.N) % d.N), o = (int)(e / ((int64_t)d.N * d.N));
+      const uint32_t* sr = reinterpret_cast<const uint32_t*>(ws + w.srow) + (i >> 5) * B;
+      const uint32_t* tr = reinterpret_cast<const uint32_t*>(ws + w.trow) + (jn >> 5) * B;
+      const float* dz = ws + w.dz0 + (int64_t)o * B;
+      float s = 0.f;
+      for (int b = 0; b < B; ++b)
+        if (((sr[b] >> (i & 31)) & (tr[b] >> (jn & 31)) & 1u) != 0u) s += dz[b];
+      G[d.off[BIL_W] + e] = s;
+      ss = s * s;
+    }
+  } else if ((blk -= w.nb_bil) == 0) {
+    // the three biases: db[o] = sum_b delta[o][b]
+    float s = 0.f;
+    int64_t at = -1;
+    if (tid < d.h0) {
+      for (int b = 0; b < B; ++b) s += ws[w.dz0 + (int64_t)tid * B + b];
+      at = d.off[BIL_B] + tid;
+    } else if (tid - 64 >= 0 && tid - 64 < d.h1) {
+      for (int b = 0; b < B; ++b) s += ws[w.dz1 + (int64_t)(tid - 64) * B + b];
+      at = d.off[L1_B] + tid - 64;
+    } else if (tid - 128 >= 0 && tid - 128 < d.A) {
+      for (int b = 0; b < B; ++b) s += act[b] == tid - 128 ? gq[b] : 0.f;
+      at = d.off[OUT_B] + tid - 128;
+    }
+    if (at >= 0) {
+      G[at] = s;
+      ss = s * s;
+    }
+  } else if ((blk -= 1) < w.nb_w1) {
+    const int tile = blk * 4 + wave;
+    if (tile < d.H1T * d.H0T) {   // (wave-uniform)
+      const int ot = tile / d.H0T, kt = tile - ot * d.H0T;
+      const float* X = ws + w.dz1;
+      const f32x4 acc = grad_tile(ws + w.y0, kt, B, lane, [&](int o, int b4) {
+        return *reinterpret_cast<const float4*>(X + (int64_t)(16 * ot + o) * B + b4);
+      });
+      const int col = 16 * kt + (lane & 15);
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const int row = 16 * ot + 4 * (lane >> 4) + v;
+        if (row < d.h1 && col < d.h0) {
+          G[d.off[L1_W] + (int64_t)row * d.h0 + col] = acc[v];
+          ss += acc[v] * acc[v];
+        }
+      }
+    }
+  } else {
+    blk -= w.nb_w1;
+    const int tile = blk * 4 + wave;
+    if (tile < d.AT * d.H1T) {
+      const int ot = tile / d.H1T, kt = tile - ot * d.H1T;
+      const f32x4 acc = grad_tile(ws + w.y1, kt, B, lane, [&](int o, int b4) {
+        const int4 ab = *reinterpret_cast<const int4*>(act + b4);
+        const float4 gb = *reinterpret_cast<const float4*>(gq + b4);
+        const int ai = 16 * ot + o;
+        return make_float4(ab.x == ai ? gb.x : 0.f, ab.y == ai ? gb.y : 0.f, ab.z == ai ? gb.z : 0.f,
+                           ab.w == ai ? gb.w : 0.f);
+      });
+      const int col = 16 * kt + (lane & 15);
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const int row = 16 * ot + 4 * (lane >> 4) + v;
+        if (row < d.A && col < d.h1) {
+          G[d.off[OUT_W] + (int64_t)row * d.h1 + col] = acc[v];
+          ss += acc[v] * acc[v];
+        }
+      }
+    }
+  }
+  red[tid] = ss;
+  __syncthreads();
+  for (int s = kGradThreads / 2; s >= 1; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  if (tid == 0) a.ws[w.partial + blockIdx.x] = red[0];
+}
+
+__global__ void __launch_bounds__(kGradThreads) ddqn_adam_kernel(LearnArgs a) {
+  __shared__ float red[kGradThreads];
+  const Dims& d = a.d;
+  const Work& w = a.w;
+  const int tid = threadIdx.x;
+  // the total norm: every block adds the same sums in the same order
+  float s = 0.f;
+  for (int k = tid; k < w.nblocks; k += kGradThreads) s += a.ws[w.partial + k];
+  red[tid] = s;
+  __syncthreads();
+  for (int k = kGradThreads / 2; k >= 1; k >>= 1) {
+    if (tid < k) red[tid] += red[tid + k];
+    __syncthreads();
+  }
+  const float total = sqrtf(red[0]);
+  // clip_grad_norm_: coef = max_norm / (total + 1e-6), at most 1; every gradient is multiplied
+  const float coef = fminf((1.f / (total + 1e-6f)) * a.max_norm, 1.f);
+  if (blockIdx.x == 0 && tid == 0) {
+    a.grad_norm[0] = total;
+    float ls = 0.f;
+    for (int b = 0; b < a.B; ++b) ls += a.ws[w.lrow + b];
+    a.loss[0] = ls / (float)a.B;
+  }
+  const float stepc = a.step[0];
+  const float bc1 = 1.f - powf(a.b1, stepc);
+  const float bc2s = sqrtf(1.f - powf(a.b2, stepc));
+  const float* G = a.ws + w.G;
+  for (int64_t e = (int64_t)blockIdx.x * kGradThreads + tid; e < d.off[TOTAL]; e += (int64_t)gridDim.x * kGradThreads) {
+    int seg = 0;
+#pragma unroll
+    for (int k = 1; k < TOTAL; ++k) seg += e >= d.off[k] ? 1 : 0;
+    if (e - d.off[seg] >= d.sz[seg]) {   // the segment's padding
+      if (a.grad) a.grad[e] = 0.f;
+      continue;
+    }
+    const float gv = G[e] * coef;
+    if (a.grad) a.grad[e] = gv;
+    const float mm = a.b1 * a.m[e] + (1.f - a.b1) * gv;
+    const float vv = a.b2 * a.v[e] + (1.f - a.b2) * gv * gv;
+    a.m[e] = mm;
+    a.v[e] = vv;
+    const float denom = sqrtf(vv) / bc2s + a.eps;
+    a.P[e] = a.P[e] - (a.lr / bc1) * mm / denom;
+  }
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+int check_batch(int64_t batch) {
+  if (batch < 16 || batch > 1024 || (batch & 15))
+    return pbn::set_error(PBN_EINVAL, "batch must be a multiple of 16 in 16..1024");
+  return PBN_OK;
+}
+
+int net_dims(const pbn_net* net, int h0, int h1, Dims* d) {
+  if (const char* msg = shape_error(1, h0, h1)) return pbn::set_error(PBN_EINVAL, msg);
+  pbn::NetView nv;
+  int rc = pbn::net_view(net, &nv);
+  if (rc) return rc;
+  if (const char* msg = shape_error(nv.n_nodes, h0, h1)) return pbn::set_error(PBN_EINVAL, msg);
+  if (nv.W < 1 || nv.W > 4) return pbn::set_error(PBN_EINVAL, "state words must be 1..4");
+  make_dims(nv.n_nodes, nv.W, nv.n_attr, h0, h1, d);
+  return PBN_OK;
+}
+
+unsigned pack_blocks(const Dims& d) { return (unsigned)std::min<int64_t>((d.itotal + 255) / 256, 4096); }
+
+}  // namespace
+
+extern "C" {
+
+int pbn_dqn_layout(int32_t n_nodes, int32_t h0, int32_t h1, int64_t* offsets) {
+  if (const char* msg = shape_error(n_nodes, h0, h1)) return pbn::set_error(PBN_EINVAL, msg);
+  if (!offsets) return pbn::set_error(PBN_EINVAL, "null offsets");
+  Dims d;
+  make_dims(n_nodes, (n_nodes + 31) / 32, 0, h0, h1, &d);
+  for (int s = 0; s <= TOTAL; ++s) offsets[s] = d.off[s];
+  return PBN_OK;
+}
+
+int pbn_dqn_image_floats(const pbn_net* net, int32_t h0, int32_t h1, int64_t* n_floats) {
+  if (!n_floats) return pbn::set_error(PBN_EINVAL, "null n_floats");
+  Dims d;
+  if (int rc = net_dims(net, h0, h1, &d)) return rc;
+  *n_floats = d.itotal;
+  return PBN_OK;
+}
+
+int pbn_dqn_pack(const pbn_net* net, int32_t h0, int32_t h1, const float* d_params, float* d_image, void* stream) {
+  Dims d;
+  if (int rc = net_dims(net, h0, h1, &d)) return rc;
+  if (!d_params || !d_image) return pbn::set_error(PBN_EINVAL, "null buffer");
+  if (!aligned16(d_params) || !aligned16(d_image))
+    return pbn::set_error(PBN_EINVAL, "parameter and image buffers: 16-byte aligned");
+  if (int rc = pbn::check_device(net)) return rc;
+  pbn::NetView nv;
+  pbn::net_view(net, &nv);
+  hipLaunchKernelGGL(dqn_pack_kernel, dim3(pack_blocks(d)), dim3(256), 0, (hipStream_t)stream, d, d_params,
+                     nv.att_first, d_image);
+  if (hipGetLastError() != hipSuccess) return pbn::set_error(PBN_EDEVICE, "dqn_pack_kernel launch failed");
+  return PBN_OK;
+}
+
+int pbn_dqn_flipmask_from_state(const pbn_net* net, uint64_t seed, uint64_t step, const uint64_t* d_step,
+                                uint64_t env_offset, int64_t n_envs, const uint32_t* d_state, const uint8_t* d_target,
+                                int32_t h0, int32_t h1, const float* d_image, float epsilon, const float* d_epsilon,
+                                float* d_q, uint32_t* d_flipmask, int32_t* d_actions, void* stream) {
+  if (n_envs < 0 || (n_envs & 31) || (env_offset & 31))
+    return pbn::set_error(PBN_EINVAL, "n_envs and env_offset must be multiples of 32");
+  if (!(epsilon >= 0.f && epsilon <= 1.f)) return pbn::set_error(PBN_EINVAL, "epsilon must be in [0, 1]");
+  if (d_step && ((uintptr_t)d_step & 7u) != 0) return pbn::set_error(PBN_EINVAL, "d_step must be 8-byte aligned");
+  if (d_epsilon && ((uintptr_t)d_epsilon & 3u) != 0) return pbn::set_error(PBN_EINVAL, "d_epsilon misaligned");
+  ActArgs a;
+  if (int rc = net_dims(net, h0, h1, &a.d)) return rc;
+  if (n_envs * (int64_t)a.d.A >= ((int64_t)1 << 31)) return pbn::set_error(PBN_EINVAL, "n_envs * n_actions >= 2^31");
+  if (!d_state || !d_target || !d_image || !d_flipmask) return pbn::set_error(PBN_EINVAL, "null buffer");
+  if (!aligned16(d_image)) return pbn::set_error(PBN_EINVAL, "d_image must be 16-byte aligned");
+  if (((uintptr_t)d_q | (uintptr_t)d_flipmask | (uintptr_t)d_actions | (uintptr_t)d_state) & 3u)
+    return pbn::set_error(PBN_EINVAL, "d_state, d_q, d_flipmask and d_actions must be 4-byte aligned");
+  if (int rc = pbn::check_device(net)) return rc;
+  if (n_envs == 0) return PBN_OK;
+  a.n = n_envs;
+  a.state = d_state;
+  a.target = d_target;
+  a.img = d_image;
+  a.seed = seed;
+  a.step = step;
+  a.env_offset = env_offset;
+  // explore iff word 0 < floor(epsilon * 2^32): epsilon = 1 always explores, 0 never
+  a.eps_u = (uint64_t)floor((double)epsilon * 4294967296.0);
+  a.d_step = d_step;
+  a.d_eps = d_epsilon;
+  a.q = d_q;
+  a.flipmask = d_flipmask;
+  a.actions = d_actions;
+  const int64_t tiles = n_envs / 16;
+  hipLaunchKernelGGL(dqn_act_kernel, dim3((unsigned)((tiles + kActWaves - 1) / kActWaves)), dim3(64 * kActWaves), 0,
+                     (hipStream_t)stream, a);
+  if (hipGetLastError() != hipSuccess) return pbn::set_error(PBN_EDEVICE, "dqn_act_kernel launch failed");
+  return PBN_OK;
+}
+
+int pbn_ddqn_learn_workspace(int32_t n_nodes, int32_t h0, int32_t h1, int64_t batch, int64_t* bytes) {
+  if (const char* msg = shape_error(n_nodes, h0, h1)) return pbn::set_error(PBN_EINVAL, msg);
+  if (int rc = check_batch(batch)) return rc;
+  if (!bytes) return pbn::set_error(PBN_EINVAL, "null bytes");
+  Dims d;
+  make_dims(n_nodes, (n_nodes + 31) / 32, 0, h0, h1, &d);
+  *bytes = make_work(d, batch).total * (int64_t)sizeof(float);
+  return PBN_OK;
+}
+
+int pbn_ddqn_learn(const pbn_net* net, int32_t h0, int32_t h1, int64_t batch, const int64_t* d_idx, int64_t capacity,
+                   const uint32_t* d_state, const uint32_t* d_next_state, const uint8_t* d_target,
+                   const int32_t* d_action, const float* d_reward, const uint8_t* d_done, float* d_params,
+                   float* d_image, const float* d_target_image, float* d_adam_m, float* d_adam_v, float* d_adam_step,
+                   float lr, float beta1, float beta2, float eps, float gamma, float max_grad_norm, void* d_workspace,
+                   int64_t workspace_bytes, float* d_loss, float* d_grad_norm, float* d_grad, const float* d_weights,
+                   float replay_constant, float* d_priority, void* stream) {
+  if ((d_weights == nullptr) != (d_priority == nullptr))
+    return pbn::set_error(PBN_EINVAL, "pbn_ddqn_learn: d_weights and d_priority come together");
+  if (((uintptr_t)d_weights | (uintptr_t)d_priority) & 3u)
+    return pbn::set_error(PBN_EINVAL, "pbn_ddqn_learn: d_weights and d_priority must be 4-byte aligned");
+  if (int rc = check_batch(batch)) return rc;
+  LearnArgs a;
+  if (int rc = net_dims(net, h0, h1, &a.d)) return rc;
+  if (capacity < 1) return pbn::set_error(PBN_EINVAL, "capacity >= 1");
+  a.w = make_work(a.d, batch);
+  if (workspace_bytes < a.w.total * (int64_t)sizeof(float))
+    return pbn::set_error(PBN_EINVAL, "workspace too small (pbn_ddqn_learn_workspace)");
+  if (!d_idx || !d_state || !d_next_state || !d_target || !d_action || !d_reward || !d_done || !d_params ||
+      !d_adam_m || !d_adam_v || !d_adam_step || !d_workspace || !d_loss || !d_grad_norm)
+    return pbn::set_error(PBN_EINVAL, "null buffer");
+  if (!d_image || !d_target_image) return pbn::set_error(PBN_EINVAL, "null network image");
+  for (const void* p : {(const void*)d_params, (const void*)d_adam_m, (const void*)d_adam_v, (const void*)d_workspace,
+                        (const void*)d_image, (const void*)d_target_image, (const void*)d_grad})
+    if (!aligned16(p)) return pbn::set_error(PBN_EINVAL, "parameter, image and workspace buffers: 16-byte aligned");
+  if (((uintptr_t)d_idx & 7u) || (((uintptr_t)d_state | (uintptr_t)d_next_state | (uintptr_t)d_action |
+                                   (uintptr_t)d_reward | (uintptr_t)d_adam_step | (uintptr_t)d_loss |
+                                   (uintptr_t)d_grad_norm) & 3u))
+    return pbn::set_error(PBN_EINVAL, "d_idx must be 8-byte, the ring and scalar buffers 4-byte aligned");
+  if (int rc = pbn::check_device(net)) return rc;
+  pbn::NetView nv;
+  pbn::net_view(net, &nv);
+  a.B = (int)batch;
+  a.idx = d_idx;
+  a.cap = capacity;
+  a.st = d_state;
+  a.nst = d_next_state;
+  a.tgt = d_target;
+  a.act = d_action;
+  a.rew = d_reward;
+  a.done = d_done;
+  a.att_first = nv.att_first;
+  a.P = d_params;
+  a.img = d_image;
+  a.timg = d_target_image;
+  a.m = d_adam_m;
+  a.v = d_adam_v;
+  a.step = d_adam_step;
+  a.lr = lr;
+  a.b1 = beta1;
+  a.b2 = beta2;
+  a.eps = eps;
+  a.gamma = gamma;
+  a.max_norm = max_grad_norm;
+  a.rconst = replay_constant;
+  a.ws = static_cast<float*>(d_workspace);
+  a.loss = d_loss;
+  a.grad_norm = d_grad_norm;
+  a.grad = d_grad;
+  a.wts = d_weights;
+  a.prio = d_priority;
+  const hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(ddqn_fb_kernel, dim3((unsigned)(batch / 16)), dim3(192), 0, s, a);
+  if (hipGetLastError() != hipSuccess) return pbn::set_error(PBN_EDEVICE, "ddqn_fb_kernel launch failed");
+  hipLaunchKernelGGL(ddqn_grad_kernel, dim3((unsigned)a.w.nblocks), dim3(kGradThreads), 0, s, a);
+  if (hipGetLastError() != hipSuccess) return pbn::set_error(PBN_EDEVICE, "ddqn_grad_kernel launch failed");
+  const unsigned ab = (unsigned)std::min<int64_t>((a.d.off[TOTAL] + kGradThreads - 1) / kGradThreads, 1024);
+  hipLaunchKernelGGL(ddqn_adam_kernel, dim3(ab), dim3(kGradThreads), 0, s, a);
+  if (hipGetLastError() != hipSuccess) return pbn::set_error(PBN_EDEVICE, "ddqn_adam_kernel launch failed");
+  hipLaunchKernelGGL(dqn_pack_kernel, dim3(pack_blocks(a.d)), dim3(256), 0, s, a.d, d_params, nv.att_first, d_image);
+  if (hipGetLastError() != hipSuccess) return pbn::set_error(PBN_EDEVICE, "dqn_pack_kernel launch failed");
+  return PBN_OK;
+}
+
+}  // extern "C"

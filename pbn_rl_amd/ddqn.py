@@ -1,0 +1,596 @@
+"""The reference's other agent, DDQN / DDQNPER (ddqn_per/, driven by train_ddqn.py), on the device.
+
+The reference steps one env per ``global_step`` (``DDQN.learn``, ddqn_per/__init__.py:308-403):
+``predict`` runs ``DQN`` on one (state, target) pair, the env takes one int action (0 is the
+no-op, :351; a > 0 flips node a - 1), the transition goes to ``ExperienceReplay`` or
+``PrioritisedER`` with ``done = terminated``, and ``_learn_step`` (:275-278, :468-483) takes one
+double-DQN / Huber / clip_grad_norm_ / Adam step.  Here one frame covers a whole ``VectorPBNEnv``:
+
+    pbn_dqn_flipmask_from_state  packed state + target id -> Q -> epsilon-greedy -> action and
+                                 flip-mask words, one launch                        (HIP, MFMA)
+    pbn_step                     the PBN transition                                 (HIP)
+    pbn_replay_store             the transitions into the device ring               (HIP)
+    pbn_per_sample / _update     prioritised replay (replay.py, csrc/pbn_per.hip)   (HIP)
+    pbn_ddqn_learn               _learn_step on a flat parameter buffer, 4 launches (HIP, MFMA)
+
+``DQN`` keeps ddqn_per/network.py's module tree and parameter names, so the ``"params"`` entry of
+a reference ``ddqn_*.pt`` loads with ``load_state_dict``.  ``ddqn_update`` restates ``_get_loss`` +
+``_back_propagate`` (with weights: ``DDQNPER._learn_step``) in PyTorch: the ``fused=False`` path
+and what tests/golden/ddqn_update.npz pins.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib
+from .replay import DeviceReplay, FusedBDQUpdate, PrioritisedDeviceReplay
+
+__all__ = ["DQN", "ddqn_update", "BatchedDDQN", "FusedDDQNUpdate", "ddqn_fused_supported", "DDQNLearner",
+           "dqn_layout", "load_ddqn_checkpoint"]
+
+
+class DQN(nn.Module):
+    """ddqn_per/network.py:11-43, same parameter names: ``input`` (nn.Bilinear(N, N, net_arch[0][0])),
+    ``linears.<i>`` (Linear(arch[0], arch[1]) per entry of ``net_arch``), ``output``; ReLU between.
+
+    On the GPU the bilinear layer y[b, o] = bias[o] + sum_ij s[b, i] W[o, i, j] g[b, j] runs as
+    two GEMMs (MyBilinear's contract form: T = g @ W.view(out * N, N)^T, then y = T.view(B, out, N)
+    @ s); on the CPU it is ``nn.Bilinear`` itself."""
+
+    def __init__(self, input_size: int, output_size: int, net_arch: Sequence[Tuple[int, int]]):
+        super().__init__()
+        net_arch = [tuple(int(x) for x in a) for a in net_arch]
+        self.input = nn.Bilinear(input_size, input_size, net_arch[0][0], bias=True)
+        self.linears = nn.ModuleList([nn.Linear(a[0], a[1], bias=True) for a in net_arch])
+        self.output = nn.Linear(self.linears[-1].out_features, output_size, bias=True)
+        self.input_size, self.output_size, self.net_arch = int(input_size), int(output_size), net_arch
+
+    def _bilinear(self, state: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        if not state.is_cuda or state.dim() < 2:
+            return self.input(state, target)
+        n, out = self.input_size, self.input.out_features
+        s2, g2 = state.reshape(-1, n), target.reshape(-1, n)
+        t = g2 @ self.input.weight.reshape(-1, n).t()                    # (B, out * N)
+        y = torch.baddbmm(self.input.bias.view(1, -1, 1), t.view(-1, out, n), s2.unsqueeze(2)).squeeze(2)
+        return y.reshape(*state.shape[:-1], out)
+
+    def forward(self, state: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        x = F.relu(self._bilinear(state, target))
+        for linear in self.linears:
+            x = F.relu(linear(x))
+        return self.output(x)
+
+
+def ddqn_update(q: nn.Module, target: nn.Module, opt: torch.optim.Optimizer, batch: Dict[str, torch.Tensor],
+                gamma: float, max_grad_norm: float, weights: Optional[torch.Tensor] = None,
+                priorities_out: Optional[torch.Tensor] = None, replay_constant: float = 1e-5):
+    """One ``_learn_step`` in PyTorch; returns (loss, total gradient norm before clipping).
+
+    ``batch``: state, target, next_state float (B, N); action int64 (B, 1); reward, done float (B, 1).
+    DDQN (ddqn_per/__init__.py:218-267): q_b = Q(s_b, g_b)[a_b], a'_b = argmax_a Q(s'_b, g_b),
+    y_b = r_b + (1 - done_b) gamma Q_target(s'_b, g_b)[a'_b], loss = mean_b huber(q_b - y_b), then
+    clip_grad_norm_ over all parameters and ``opt.step()``.  With ``weights`` (float32 [B];
+    DDQNPER._learn_step, :468-483): l_b = w_b h_b, loss = mean_b l_b and ``priorities_out``
+    (float32 [B], optional) receives |l_b| + ``replay_constant``."""
+    if weights is None and priorities_out is not None:
+        raise ValueError("priorities_out needs weights")
+    with torch.no_grad():
+        action_prime = q(batch["next_state"], batch["target"]).max(dim=1)[1].unsqueeze(1)
+        target_q = batch["reward"] + (1 - batch["done"]) * gamma * target(
+            batch["next_state"], batch["target"]).gather(1, action_prime)
+    controller_q = q(batch["state"], batch["target"]).gather(1, batch["action"])
+    if weights is None:
+        loss = F.huber_loss(controller_q, target_q, reduction="mean")
+    else:
+        loss = F.huber_loss(controller_q, target_q, reduction="none") * weights.reshape(-1, 1)
+        if priorities_out is not None:
+            priorities_out.copy_(loss.detach().squeeze(1).abs() + replay_constant)
+        loss = loss.mean()
+    opt.zero_grad()
+    loss.backward()
+    norm = torch.nn.utils.clip_grad_norm_(q.parameters(), max_grad_norm)
+    opt.step()
+    return loss.detach(), norm.detach()
+
+
+def dqn_layout(n_nodes: int, h0: int, h1: int) -> List[int]:
+    """pbn_dqn_layout: the float offsets of the flat parameter buffer's 6 segments, then its size."""
+    off = (ctypes.c_int64 * 7)()
+    _lib.check(_lib.load().pbn_dqn_layout(n_nodes, h0, h1, off), "pbn_dqn_layout")
+    return list(off)
+
+
+def ddqn_fused_supported(n_nodes: int, net_arch, batch_size: int) -> bool:
+    """Whether pbn_ddqn_learn runs this shape (its workspace query accepts it): one hidden Linear
+    with both widths <= 64, N + 1 <= 128, a batch that is a multiple of 16 and <= 1024."""
+    arch = [tuple(a) for a in net_arch]
+    if len(arch) != 1 or len(arch[0]) != 2:
+        return False
+    h0, h1 = int(arch[0][0]), int(arch[0][1])
+    nbytes = ctypes.c_int64()
+    return _lib.load().pbn_ddqn_learn_workspace(int(n_nodes), h0, h1, int(batch_size), ctypes.byref(nbytes)) == 0
+
+
+def _segments(q: DQN):
+    """The parameters in pbn_dqn_layout's segment order."""
+    lin = q.linears[0]
+    return [q.input.weight, q.input.bias, lin.weight, lin.bias, q.output.weight, q.output.bias]
+
+
+def _check_dqn(q: DQN, n_nodes: int) -> Tuple[int, int]:
+    if not isinstance(q, DQN) or q.input_size != n_nodes or q.output_size != n_nodes + 1:
+        raise ValueError("needs a DQN(N, N + 1, net_arch) for the env's N")
+    if len(q.linears) != 1:
+        raise ValueError("the HIP kernels run one hidden Linear (len(net_arch) == 1)")
+    return int(q.linears[0].in_features), int(q.linears[0].out_features)
+
+
+def _first_states(spec, device) -> torch.Tensor:
+    """(256, N) float32: row t = the first state of attractor t, zeros past them (target id 255)."""
+    tab = torch.zeros(256, spec.n, dtype=torch.float32)
+    for t, a in enumerate(spec.attractors):
+        tab[t] = torch.tensor(list(a[0]), dtype=torch.float32)
+    return tab.to(device)
+
+
+def _unpack(words: torch.Tensor, n_nodes: int) -> torch.Tensor:
+    """Packed state words (W, B) int32 -> (B, N) float32 (bit i of word w = node 32 w + i)."""
+    sh = torch.arange(32, device=words.device, dtype=torch.int32)
+    bits = (words.t().unsqueeze(2) >> sh) & 1
+    return bits.reshape(words.shape[1], -1)[:, :n_nodes].to(torch.float32)
+
+
+class BatchedDDQN:
+    """DDQN.predict (ddqn_per/__init__.py:155-179) for a whole VectorPBNEnv.  ``act_q`` is one
+    launch, pbn_dqn_flipmask_from_state: packed state + target id -> Q -> epsilon-greedy ->
+    ``self.actions`` (int32 [n]) and ``env.flipmask``.  Epsilon-greedy follows the EXPLORE law of
+    pbn_q_to_flipmask with one branch, so the actions equal that kernel's on the same Q.
+
+    The kernel reads the network's image (pbn_dqn_pack); it is rebuilt when the parameters'
+    version counters change, or supplied by a learner (``image_provider``, FusedDDQNUpdate).
+    ``kernel`` (default: whenever the kernel takes the network, i.e. one hidden Linear, widths <= 64,
+    N + 1 <= 128): False runs ``DQN.forward`` on pbn_obs_unpack's observation and pbn_q_to_flipmask
+    instead (the PyTorch path, also the baseline of tools/ddqn_bench.py); True with another network
+    is an error.  An env that is not on the GPU (a test stub) acts in PyTorch."""
+
+    def __init__(self, env, dqn: Optional[DQN] = None, *, net_arch=((50, 50),), epsilon: float = 0.0,
+                 kernel: Optional[bool] = None, generator: Optional[torch.Generator] = None):
+        self.env = env
+        N = env.n_nodes
+        self.q = dqn if dqn is not None else DQN(N, N + 1, list(net_arch))
+        self.q = self.q.to(env.device)
+        if self.q.input_size != N or self.q.output_size != N + 1:
+            raise ValueError("needs a DQN(N, N + 1, net_arch) for the env's N")
+        self.epsilon = float(epsilon)
+        self.on_gpu = torch.device(env.device).type == "cuda"
+        supported = self.on_gpu and len(self.q.linears) == 1 and ddqn_fused_supported(N, self.q.net_arch, 16)
+        if kernel and not supported:
+            raise ValueError("the acting kernel needs a GPU env and one hidden Linear, widths <= 64, N + 1 <= 128")
+        self.kernel = supported if kernel is None else bool(kernel)
+        n = env.n_alloc
+        self.actions = torch.zeros(n, dtype=torch.int32, device=env.device)
+        self.qbuf = torch.empty(n, N + 1, dtype=torch.float32, device=env.device)
+        self.first = _first_states(env.spec, env.device)
+        self.image_provider = None
+        self.gen = generator
+        self._key = None
+        if self.kernel:
+            self.h0, self.h1 = _check_dqn(self.q, N)
+            self.off = dqn_layout(N, self.h0, self.h1)
+            self._flat = torch.zeros(self.off[6], dtype=torch.float32, device=env.device)
+            nimg = ctypes.c_int64()
+            _lib.check(_lib.load().pbn_dqn_image_floats(env.net.handle, self.h0, self.h1, ctypes.byref(nimg)),
+                       "pbn_dqn_image_floats")
+            self._image = torch.zeros(nimg.value, dtype=torch.float32, device=env.device)
+        elif self.on_gpu:
+            self.obs = torch.empty(2, n, N, dtype=torch.float32, device=env.device)
+
+    def image(self) -> torch.Tensor:
+        """The network image the acting kernel reads, up to date with the parameters."""
+        if self.image_provider is not None:
+            return self.image_provider()
+        params = _segments(self.q)
+        key = tuple((p.data_ptr(), p._version) for p in params)
+        if key != self._key:
+            with torch.no_grad():
+                for p, at in zip(params, self.off):
+                    self._flat[at:at + p.numel()].copy_(p.detach().reshape(-1))
+            env = self.env
+            with torch.cuda.device(env.device):
+                _lib.check(_lib.load().pbn_dqn_pack(env.net.handle, self.h0, self.h1, self._flat.data_ptr(),
+                                                    self._image.data_ptr(), env._stream()), "pbn_dqn_pack")
+            self._key = key
+        return self._image
+
+    def observe(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(state, target) float32 (n, N) each: the envs' states and their targets' first states."""
+        env = self.env
+        if not self.on_gpu or self.kernel:
+            return _unpack(env.state, env.n_nodes), self.first[env.target.long()]
+        with torch.cuda.device(env.device):
+            _lib.check(_lib.load().pbn_obs_unpack(env.net.handle, env.n_alloc, env.state.data_ptr(),
+                                                  env.target.data_ptr(), self.obs.data_ptr(), env._stream()),
+                       "pbn_obs_unpack")
+        return self.obs[0], self.obs[1]
+
+    def _launch(self, eps: float, step_t, epsilon_t, q_out) -> None:
+        env = self.env
+        image = self.image()
+        with torch.cuda.device(env.device):
+            _lib.check(_lib.load().pbn_dqn_flipmask_from_state(
+                env.net.handle, env.seed, env.step_index, step_t.data_ptr() if step_t is not None else None,
+                env.env_offset, env.n_alloc, env.state.data_ptr(), env.target.data_ptr(), self.h0, self.h1,
+                image.data_ptr(), eps, epsilon_t.data_ptr() if epsilon_t is not None else None,
+                q_out.data_ptr() if q_out is not None else None, env.flipmask.data_ptr(), self.actions.data_ptr(),
+                env._stream()), "pbn_dqn_flipmask_from_state")
+
+    @torch.no_grad()
+    def q_values(self) -> torch.Tensor:
+        """Q (n, N + 1) of every env's (state, target); with the kernel, its own Q output (the
+        launch also rewrites ``actions`` and ``env.flipmask`` at the agent's epsilon)."""
+        if self.kernel:
+            self._launch(self.epsilon, None, None, self.qbuf)
+            return self.qbuf
+        s, g = self.observe()
+        return self.q(s, g)
+
+    @torch.no_grad()
+    def act_q(self, epsilon: Optional[float] = None, step_t: Optional[torch.Tensor] = None,
+              epsilon_t: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Epsilon-greedy actions of every env at the env's next step index -> ``env.flipmask`` and
+        ``self.actions``.  ``step_t`` / ``epsilon_t``: optional one-element device tensors (int64 /
+        float32) read when the kernel runs (graph replays)."""
+        if step_t is not None and (step_t.dtype != torch.int64 or step_t.numel() != 1):
+            raise ValueError("step_t must be a one-element int64 tensor")
+        if epsilon_t is not None and (epsilon_t.dtype != torch.float32 or epsilon_t.numel() != 1):
+            raise ValueError("epsilon_t must be a one-element float32 tensor")
+        env = self.env
+        eps = self.epsilon if epsilon is None else float(epsilon)
+        if self.kernel:
+            self._launch(eps, step_t, epsilon_t, None)
+            return env.flipmask
+        q = self.q_values().contiguous()
+        if self.on_gpu:
+            L = _lib.load()
+            with torch.cuda.device(env.device):
+                if step_t is None:
+                    _lib.check(L.pbn_q_to_flipmask(env.net.handle, env.seed, env.step_index, env.env_offset,
+                                                   env.n_alloc, 1, env.n_nodes + 1, q.data_ptr(), eps,
+                                                   env.flipmask.data_ptr(), self.actions.data_ptr(), env._stream()),
+                               "pbn_q_to_flipmask")
+                else:
+                    _lib.check(L.pbn_q_to_flipmask_dev(env.net.handle, env.seed, step_t.data_ptr(), env.env_offset,
+                                                       env.n_alloc, 1, env.n_nodes + 1, q.data_ptr(), eps,
+                                                       epsilon_t.data_ptr() if epsilon_t is not None else None,
+                                                       env.flipmask.data_ptr(), self.actions.data_ptr(),
+                                                       env._stream()), "pbn_q_to_flipmask_dev")
+            return env.flipmask
+        # no GPU (a stub env): torch's generator explores
+        n, A = q.shape
+        explore = torch.rand(n, generator=self.gen) < eps
+        rand = torch.randint(0, A, (n,), generator=self.gen)
+        a = torch.where(explore, rand, q.argmax(1)).to(torch.int32)
+        self.actions.copy_(a)
+        node = (a - 1).clamp(min=0)
+        words = torch.arange(env.words, dtype=torch.int32).unsqueeze(1)
+        bit = torch.ones_like(node) << (node & 31)
+        env.flipmask.copy_(torch.where((a > 0).unsqueeze(0) & ((node >> 5).unsqueeze(0) == words), bit.unsqueeze(0),
+                                       torch.zeros_like(bit).unsqueeze(0)))
+        return env.flipmask
+
+    @torch.no_grad()
+    def step(self, epsilon: Optional[float] = None):
+        """One frame for every env; returns (state', reward, flags) views as VectorPBNEnv.step_flipmask."""
+        self.act_q(epsilon)
+        return self.env.step_flipmask(use_current=True)
+
+
+class FusedDDQNUpdate:
+    """``_learn_step`` (ddqn_per/__init__.py:275-278, :468-483) as pbn_ddqn_learn's four HIP launches
+    instead of PyTorch's forward / autograd / clip / Adam kernels.
+
+    The online network's parameters move into one flat fp32 buffer (``pbn_dqn_layout``) and become
+    views of it, and so do the target's; ``state_dict``, the PyTorch forward and the kernels see the
+    same weights.  Each network has an image (``q_image`` / ``t_image``, pbn_dqn_pack): the bilinear
+    layer contracted with every attractor's first state, the padded biases and the dense weights
+    as MFMA-fragment tiles.  Every update rewrites the online image; ``pack()`` rebuilds the images
+    after weights change any other way (a loaded checkpoint); ``sync_target()`` is the hard target
+    copy (:286-287), parameters and image, device to device.  Adam (torch.optim.Adam's arithmetic)
+    keeps its moments in buffers of the same layout and its step count on the device."""
+
+    def __init__(self, q: DQN, target: DQN, net, *, batch_size: int, learning_rate: float = 1e-4,
+                 gamma: float = 0.95, max_grad_norm: float = 10.0, betas=(0.9, 0.999), eps: float = 1e-8,
+                 keep_grad: bool = False):
+        N = net.spec.n
+        dev = next(q.parameters()).device
+        if dev.type != "cuda":
+            raise ValueError("FusedDDQNUpdate runs on the GPU")
+        self.h0, self.h1 = _check_dqn(q, N)
+        if _check_dqn(target, N) != (self.h0, self.h1):
+            raise ValueError("the target network must have the online network's shape")
+        if not ddqn_fused_supported(N, [(self.h0, self.h1)], batch_size):
+            raise ValueError("pbn_ddqn_learn: one hidden Linear, widths <= 64, N + 1 <= 128, batch a multiple "
+                             "of 16 and <= 1024")
+        self.net, self.N, self.B = net, N, int(batch_size)
+        self.lr, self.gamma, self.max_grad_norm = float(learning_rate), float(gamma), float(max_grad_norm)
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        self.off = dqn_layout(N, self.h0, self.h1)
+        self.q, self.target = q, target
+        self.q_flat = self._flatten(q, dev)
+        self.t_flat = self._flatten(target, dev)
+        self._qp, self._tp = _segments(q), _segments(target)
+        self._qv = self._tv = None
+        self.m = torch.zeros_like(self.q_flat)
+        self.v = torch.zeros_like(self.q_flat)
+        self.step = torch.zeros(1, dtype=torch.float32, device=dev)
+        L = _lib.load()
+        nimg, nbytes = ctypes.c_int64(), ctypes.c_int64()
+        _lib.check(L.pbn_dqn_image_floats(net.handle, self.h0, self.h1, ctypes.byref(nimg)), "pbn_dqn_image_floats")
+        self.q_image = torch.zeros(nimg.value, dtype=torch.float32, device=dev)
+        self.t_image = torch.zeros_like(self.q_image)
+        _lib.check(L.pbn_ddqn_learn_workspace(N, self.h0, self.h1, self.B, ctypes.byref(nbytes)),
+                   "pbn_ddqn_learn_workspace")
+        self.work = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=dev)
+        self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.grad_norm = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.grad = torch.zeros_like(self.q_flat) if keep_grad else None
+        self.pack()
+
+    def _flatten(self, q: DQN, dev) -> torch.Tensor:
+        flat = torch.zeros(self.off[6], dtype=torch.float32, device=dev)
+        with torch.no_grad():
+            for p, at in zip(_segments(q), self.off):
+                view = flat[at:at + p.numel()].view(p.shape)
+                view.copy_(p.detach())
+                p.data = view
+        return flat
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.q_flat.device).cuda_stream
+
+    _versions = staticmethod(FusedBDQUpdate._versions)
+    _bump = staticmethod(FusedBDQUpdate._bump)
+
+    def pack(self, which: str = "both") -> None:
+        """Recompute the image (pbn_dqn_pack) of the online and/or target network."""
+        L = _lib.load()
+        with torch.cuda.device(self.q_flat.device):
+            for name, flat, image in (("online", self.q_flat, self.q_image), ("target", self.t_flat, self.t_image)):
+                if which in ("both", name):
+                    _lib.check(L.pbn_dqn_pack(self.net.handle, self.h0, self.h1, flat.data_ptr(), image.data_ptr(),
+                                              self._stream()), "pbn_dqn_pack")
+        if which in ("both", "online"):
+            self._qv = self._versions(self._qp)
+        if which in ("both", "target"):
+            self._tv = self._versions(self._tp)
+
+    def sync(self) -> None:
+        """Repack the image of a network whose parameters changed since its last pack (e.g. a
+        load_state_dict); a no-op otherwise."""
+        if self._versions(self._qp) != self._qv:
+            self.pack("online")
+        if self._versions(self._tp) != self._tv:
+            self.pack("target")
+
+    def mark_updated(self) -> None:
+        """After a pbn_ddqn_learn launch: the online parameters changed in place."""
+        self._bump(self._qp)
+        self._qv = self._versions(self._qp)
+
+    def sync_target(self) -> None:
+        """target <- online (``self.target.load_state_dict(self.controller.state_dict())``,
+        ddqn_per/__init__.py:286-287): the parameters and the image, two pbn_copy_async launches."""
+        self.sync()
+        L = _lib.load()
+        with torch.cuda.device(self.q_flat.device):
+            _lib.check(L.pbn_copy_async(self.t_flat.data_ptr(), self.q_flat.data_ptr(), self.q_flat.numel() * 4,
+                                        self._stream()), "pbn_copy_async")
+            _lib.check(L.pbn_copy_async(self.t_image.data_ptr(), self.q_image.data_ptr(), self.q_image.numel() * 4,
+                                        self._stream()), "pbn_copy_async")
+        self._bump(self._tp)
+        self._tv = self._versions(self._tp)
+
+    def acting_image(self) -> torch.Tensor:
+        """BatchedDDQN's image provider: the online image, repacked first if the weights were
+        changed outside update()."""
+        self.sync()
+        return self.q_image
+
+    def update(self, replay: DeviceReplay, idx: torch.Tensor, weights: Optional[torch.Tensor] = None,
+               priorities_out: Optional[torch.Tensor] = None, replay_constant: float = 1e-5) -> torch.Tensor:
+        """One update on ring rows ``idx`` (int64, ``batch_size`` of them); returns the loss buffer's
+        element (overwritten by the next update; ``grad_norm`` holds the total norm before
+        clipping).  ``weights`` / ``priorities_out`` (float32 [B] on the device, both or neither):
+        DDQNPER's importance weights by batch position in, |w_b h_b| + ``replay_constant`` out."""
+        if idx.shape != (self.B,) or idx.dtype != torch.int64:
+            raise ValueError(f"idx must be {self.B} int64 ring indices")
+        if replay.action.shape[1] != 1:
+            raise ValueError("the replay ring must hold one action per transition")
+        FusedBDQUpdate.check_per_args(self.B, self.q_flat.device, weights, priorities_out)
+        self.sync()
+        b1, b2 = self.betas
+        with torch.cuda.device(self.q_flat.device):
+            _lib.check(_lib.load().pbn_ddqn_learn(
+                self.net.handle, self.h0, self.h1, self.B, idx.contiguous().data_ptr(), replay.capacity,
+                replay.state.data_ptr(), replay.next_state.data_ptr(), replay.target.data_ptr(),
+                replay.action.data_ptr(), replay.reward.data_ptr(), replay.done.data_ptr(), self.q_flat.data_ptr(),
+                self.q_image.data_ptr(), self.t_image.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+                self.step.data_ptr(), self.lr, b1, b2, self.eps, self.gamma, self.max_grad_norm,
+                self.work.data_ptr(), self.work.numel() * 4, self.loss.data_ptr(), self.grad_norm.data_ptr(),
+                self.grad.data_ptr() if self.grad is not None else None,
+                weights.data_ptr() if weights is not None else None, float(replay_constant),
+                priorities_out.data_ptr() if priorities_out is not None else None, self._stream()), "pbn_ddqn_learn")
+        if not torch.cuda.is_current_stream_capturing():
+            self.mark_updated()
+        return self.loss[0]
+
+    def grads(self) -> List[torch.Tensor]:
+        """The last update's clipped gradient (keep_grad=True) as views shaped like q.parameters()."""
+        if self.grad is None:
+            raise ValueError("construct with keep_grad=True")
+        g = {id(p): self.grad[at:at + p.numel()].view(p.shape) for p, at in zip(self._qp, self.off)}
+        return [g[id(p)] for p in self.q.parameters()]
+
+
+class DDQNLearner:
+    """``DDQN.learn`` / ``DDQNPER`` (ddqn_per/__init__.py:308-403, :431-539) over a VectorPBNEnv; the
+    defaults are train_ddqn.py's.  One ``frame()`` is one reference ``global_step`` for every env:
+    act at the current epsilon, step, store all ``n_alloc`` transitions with ``done`` = TERMINATED
+    only (:380-389), one ``_learn_step`` if ``frames > learning_starts``, ``frame % train_frequency
+    == 0`` and the ring holds ``batch_size`` rows, then the schedules of ``_schedule_step``
+    (:283-290, :488-490): epsilon down by (max - min) / (exploration_fraction total_frames) to
+    ``min_epsilon``, the hard target copy when ``(frame + 1) % target_update == 0``, and beta up by
+    (max_beta - beta) / (beta_fraction total_frames) to 1 -- every frame, learning or not, so the
+    sample of frame f uses the reference's BETA at that global_step.
+
+    ``prioritised=True`` (GPU only): every update is PrioritisedDeviceReplay.sample -> the update
+    with importance weights -> update_priorities with |w_b h_b| + ``replay_constant``.
+    ``fused`` (default: when ``ddqn_fused_supported`` and the env is on the GPU) runs acting and the
+    update as the HIP launches of csrc/pbn_ddqn.hip; ``fused=False`` acts through ``DQN.forward``
+    and updates with ``ddqn_update`` + torch.optim.Adam."""
+
+    def __init__(self, env, dqn: Optional[DQN] = None, *, net_arch=((50, 50),), total_frames: int,
+                 capacity: int, batch_size: int = 64, target_update: int = 512, gamma: float = 0.95,
+                 max_epsilon: float = 1.0, min_epsilon: float = 0.05, exploration_fraction: float = 0.1,
+                 learning_rate: float = 1e-4, max_grad_norm: float = 10.0, learning_starts: int = 0,
+                 train_frequency: int = 1, prioritised: bool = True, per_alpha: float = 0.6, per_beta: float = 0.4,
+                 per_max_beta: float = 1.0, beta_fraction: float = 0.75, replay_constant: float = 1e-5,
+                 fused: Optional[bool] = None, seed: int = 0):
+        dev = torch.device(env.device)
+        on_gpu = dev.type == "cuda"
+        if prioritised and not on_gpu:
+            raise ValueError("prioritised replay runs on the GPU")
+        if prioritised and batch_size > 1024:
+            raise ValueError("prioritised replay samples at most 1024 rows per update")
+        if not env.keep_final_state:
+            raise ValueError("DDQNLearner needs the env's final_state (keep_final_state=True)")
+        N = env.n_nodes
+        self.env = env
+        q = dqn if dqn is not None else DQN(N, N + 1, list(net_arch))
+        can_fuse = on_gpu and len(q.linears) == 1 and ddqn_fused_supported(N, q.net_arch, batch_size)
+        if fused and not can_fuse:
+            raise ValueError("fused update: a GPU env and a shape ddqn_fused_supported accepts")
+        use_fused = can_fuse if fused is None else bool(fused)
+        self.gen = torch.Generator(device=dev)
+        self.gen.manual_seed(seed)
+        self.agent = BatchedDDQN(env, q, kernel=use_fused, generator=self.gen)
+        self.q = self.agent.q.train()
+        self.target = DQN(N, N + 1, self.q.net_arch).to(dev)
+        self.target.load_state_dict(self.q.state_dict())
+        self.fused: Optional[FusedDDQNUpdate] = None
+        self.opt = None
+        if use_fused:
+            self.fused = FusedDDQNUpdate(self.q, self.target, env.net, batch_size=batch_size,
+                                         learning_rate=learning_rate, gamma=gamma, max_grad_norm=max_grad_norm)
+            self.agent.image_provider = self.fused.acting_image
+        else:
+            self.opt = torch.optim.Adam(self.q.parameters(), lr=learning_rate)
+        cap = max(int(capacity), env.n_alloc)
+        self.prioritised = bool(prioritised)
+        if self.prioritised:
+            # beta is set before every sample (the reference moves it per global_step, not per sample)
+            self.replay = PrioritisedDeviceReplay(cap, env.words, 1, dev, alpha=per_alpha, beta=per_beta,
+                                                  max_beta=per_max_beta, beta_step=0.0, seed=seed)
+            self._prio = torch.empty(batch_size, dtype=torch.float32, device=dev)
+        else:
+            self.replay = DeviceReplay(cap, env.words, 1, dev)
+        self._pos_t = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._size_t = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.first = self.agent.first
+        self.total_frames = int(total_frames)
+        self.batch_size, self.gamma, self.target_update = int(batch_size), float(gamma), int(target_update)
+        self.max_grad_norm, self.replay_constant = float(max_grad_norm), float(replay_constant)
+        self.learning_starts, self.train_frequency = int(learning_starts), int(train_frequency)
+        self.epsilon, self.min_epsilon = float(max_epsilon), float(min_epsilon)
+        self.epsilon_decrement = (max_epsilon - min_epsilon) / (exploration_fraction * total_frames)
+        self.beta = float(per_beta)
+        self.beta_increment = (per_max_beta - per_beta) / (beta_fraction * total_frames)
+        self.frames = 0
+        self.updates = 0
+        self.syncs: List[int] = []          # the frames whose schedule step copied the target
+        self.last_loss: Optional[torch.Tensor] = None
+        self.last_beta: Optional[float] = None   # the beta of the last prioritised sample
+
+    def gather(self, idx: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """Rows ``idx`` of the ring as ``ddqn_update``'s batch (pbn_replay_batch when it takes the
+        batch size, else PyTorch bit operations)."""
+        rp, N, B = self.replay, self.env.n_nodes, idx.shape[0]
+        if rp.device.type == "cuda" and B % 32 == 0:
+            b = rp.gather(idx, self.env.net)
+            x = b["x"]
+            return {"state": x[0, :B], "target": x[1, :B], "next_state": x[0, B:], "action": b["actions"].view(B, 1),
+                    "reward": b["rewards"], "done": b["masks"]}
+        return {"state": _unpack(rp.state[:, idx], N), "target": self.first[rp.target[idx].long()],
+                "next_state": _unpack(rp.next_state[:, idx], N), "action": rp.action[idx].long().view(B, 1),
+                "reward": rp.reward[idx].view(B, 1), "done": rp.done[idx].to(torch.float32).view(B, 1)}
+
+    def _learn_step(self) -> torch.Tensor:
+        rp, B = self.replay, self.batch_size
+        if self.prioritised:
+            rp.beta_t.fill_(self.beta)
+            rp.beta = self.last_beta = self.beta
+            idx, w = rp.sample(B)
+            if self.fused is not None:
+                loss = self.fused.update(rp, idx, weights=w, priorities_out=self._prio,
+                                         replay_constant=self.replay_constant)
+            else:
+                loss, _ = ddqn_update(self.q, self.target, self.opt, self.gather(idx), self.gamma, self.max_grad_norm,
+                                      weights=w, priorities_out=self._prio, replay_constant=self.replay_constant)
+            rp.update_priorities(idx, self._prio)
+            return loss
+        idx = rp.sample_indices(B, self.gen)
+        if self.fused is not None:
+            return self.fused.update(rp, idx)
+        return ddqn_update(self.q, self.target, self.opt, self.gather(idx), self.gamma, self.max_grad_norm)[0]
+
+    def sync_target(self) -> None:
+        if self.fused is not None:
+            self.fused.sync_target()
+        else:
+            self.target.load_state_dict(self.q.state_dict())
+
+    def frame(self):
+        """One global_step for every env; returns (reward, done) of the ``num_envs`` envs, ``done``
+        = terminated or truncated (the episode ended; what is stored is terminated alone)."""
+        env, rp = self.env, self.replay
+        f = self.frames
+        state = env.state.clone()
+        target = env.target.clone()
+        self.agent.act_q(self.epsilon)
+        _, reward, flags = env.step_flipmask(use_current=True)
+        rp.store_at(self._pos_t, self._size_t, state, target, self.agent.actions.view(-1, 1), env.reward,
+                    env.final_state, env.flags, done_mask=_lib.FLAG_TERMINATED)
+        rp.pos = (rp.pos + env.n_alloc) % rp.capacity
+        rp.size = min(rp.size + env.n_alloc, rp.capacity)
+        if f > self.learning_starts and f % self.train_frequency == 0 and rp.size >= max(self.batch_size, 2):
+            self.last_loss = self._learn_step()
+            self.updates += 1
+        # _schedule_step
+        self.epsilon = max(self.min_epsilon, self.epsilon - self.epsilon_decrement)
+        if (f + 1) % self.target_update == 0:
+            self.sync_target()
+            self.syncs.append(f)
+        self.beta = min(self.beta + self.beta_increment, 1)
+        self.frames = f + 1
+        done = (flags & (_lib.FLAG_TERMINATED | _lib.FLAG_TRUNCATED)) != 0
+        return reward, done
+
+
+def load_ddqn_checkpoint(path: str) -> DQN:
+    """A ``DQN`` from the ``.npz`` export of a reference save dict (``DDQN._make_save_dict``,
+    ddqn_per/__init__.py:130-148; tools/export_agent.py --ddqn): arrays ``params.<name>`` (the
+    ``"params"`` state dict), ``net_arch`` (``policy_kwargs["net_arch"]``, int (L, 2)), ``input_size``
+    and ``output_size``.  Arrays only; nothing in the file is executed."""
+    with np.load(path, allow_pickle=False) as z:
+        arch = [tuple(int(x) for x in row) for row in np.asarray(z["net_arch"]).reshape(-1, 2)]
+        dqn = DQN(int(z["input_size"]), int(z["output_size"]), arch)
+        sd = {k[len("params."):]: torch.from_numpy(np.asarray(z[k], dtype=np.float32)) for k in z.files
+              if k.startswith("params.")}
+    dqn.load_state_dict(sd)
+    return dqn

@@ -214,7 +214,8 @@ def evaluate_control(env_or_spec, model, *, attractors=None, pairs=None, runs: i
     ``attractors`` (default: the spec's) are the evaluation's attractor set, in the order the
     result matrix is indexed; ``pairs`` as ``plan_pairs``.
     ``model``: a BranchingQNetwork, acting greedily through ``BatchedBDQ.act_q`` (one fused launch;
-    ``fused=False``: the torch module on the unpacked observation), or a policy
+    ``fused=False``: the torch module on the unpacked observation), a DQN (ddqn.py; one branch,
+    greedy through ``BatchedDDQN.act_q``), or a policy
     ``(state_bits (n, N) uint8, target_bits (n, N) uint8) -> (n, k)`` actions in [0, N] on the GPU.
     ``graph``: capture one protocol step after a first eager one and replay it (a policy that
     synchronises cannot be captured: pass ``graph=False``).  ``poll``: the number of open runs is
@@ -225,6 +226,7 @@ def evaluate_control(env_or_spec, model, *, attractors=None, pairs=None, runs: i
 
     from . import _lib
     from .agent import BatchedBDQ, BranchingQNetwork
+    from .ddqn import DQN, BatchedDDQN
     from .ssd import _spec_of
     from .vector_env import VectorPBNEnv, actions_to_flipmask, unpack_states
 
@@ -276,6 +278,13 @@ def evaluate_control(env_or_spec, model, *, attractors=None, pairs=None, runs: i
                     bdq.act_q(epsilon=0.0, step_t=step_t)
                 else:
                     bdq.act_dev(bdq.q(bdq.observe()), step_t, epsilon=0.0)
+        elif isinstance(model, DQN):
+            # one branch, greedy (DDQN.predict(deterministic=True), ddqn_per/__init__.py:155-179)
+            ddqn = BatchedDDQN(venv, copy.deepcopy(model), epsilon=0.0)
+            buf["actions"] = ddqn.actions.view(n, 1)
+
+            def act(check: bool) -> None:
+                ddqn.act_q(epsilon=0.0, step_t=step_t)
         elif callable(model):
             tbits = to_dev(plan.target_bits[:n_real], torch.uint8)
 
@@ -288,7 +297,7 @@ def evaluate_control(env_or_spec, model, *, attractors=None, pairs=None, runs: i
                     buf["actions"] = torch.zeros(n, a.shape[1], dtype=torch.int32, device=dev)
                 buf["actions"][:n_real].copy_(a)
         else:
-            raise TypeError("model must be a BranchingQNetwork or a callable policy")
+            raise TypeError("model must be a BranchingQNetwork, a DQN or a callable policy")
 
         def track() -> None:
             actions = buf["actions"]

@@ -29,6 +29,24 @@ def export(model: str) -> str:
     return out
 
 
+def export_ddqn(pt_path: str, out: str) -> str:
+    """python tools/export_agent.py --ddqn ddqn_25000.pt ddqn_25000.npz: a reference DDQN / DDQNPER
+    save dict (ddqn_per/__init__.py:130-153; a pickled dict, so load only your own files) as the arrays
+    pbn_rl_amd.ddqn.load_ddqn_checkpoint reads: params.<name>, net_arch, input_size, output_size."""
+    import numpy as np
+    sd = torch.load(pt_path, map_location="cpu", weights_only=False)
+    arrays = {"params." + k: v.detach().to(torch.float32).numpy() for k, v in sd["params"].items()}
+    arrays["net_arch"] = np.array(sd["policy_kwargs"]["net_arch"], dtype=np.int64).reshape(-1, 2)
+    arrays["input_size"] = np.int64(sd["input_size"])
+    arrays["output_size"] = np.int64(sd["output_size"])
+    np.savez(out, **arrays)
+    print("wrote", out, sum(v.size for v in arrays.values()), "values")
+    return out
+
+
 if __name__ == "__main__":
-    for m in sys.argv[1:] or ["pbn7"]:
-        export(m)
+    if sys.argv[1:2] == ["--ddqn"]:
+        export_ddqn(sys.argv[2], sys.argv[3])
+    else:
+        for m in sys.argv[1:] or ["pbn7"]:
+            export(m)
