@@ -763,6 +763,27 @@ int pbn_ddqn_learn(const pbn_net* net, int32_t h0, int32_t h1, int64_t batch, co
                    int64_t workspace_bytes, float* d_loss, float* d_grad_norm, float* d_grad, const float* d_weights,
                    float replay_constant, float* d_priority, void* stream);
 
+/*
+ * pbn_ddqn_schedule: the device half of _schedule_step (ddqn_per/__init__.py:283-290, :488-490) for a
+ * learning frame replayed from a hipGraph (pbn_rl_amd/ddqn.py DDQNLearner.capture).  An additive
+ * export (the ABI version is unchanged).  One launch, placed after pbn_ddqn_learn's:
+ *   *d_beta = min(*d_beta + beta_increment, 1.0) in fp64 (DDQNPER's increment_beta, :488-490, on the
+ *     double pbn_per_sample reads);
+ *   when (*d_step - step_base) mod target_update == 0, the hard target copy (:286-287):
+ *     d_target_params[0 .. n_params) <- d_params and d_target_image[0 .. n_image) <- d_image, floats,
+ *     as 16-byte vector loads and stores; otherwise every block exits after reading *d_step.
+ * d_step is the env step index that pbn_replay_advance advanced earlier in the same frame, and
+ * step_base its value before the learner's frame 0, so *d_step - step_base counts the frames done
+ * and the copy falls on the frames f with (f + 1) mod target_update == 0.  The launch does not write
+ * *d_step, so all its blocks decide alike, on every replay.  d_beta and d_step 8-byte, the four
+ * buffers 16-byte aligned; n_params and n_image positive multiples of 4 (pbn_dqn_layout's and
+ * pbn_dqn_image_floats' sizes are multiples of 16); target_update >= 1; a target buffer must not
+ * overlap its source.  No atomics; nothing is allocated or synchronised.
+ */
+int pbn_ddqn_schedule(double* d_beta, double beta_increment, const int64_t* d_step, int64_t step_base,
+                      int64_t target_update, float* d_target_params, const float* d_params, int64_t n_params,
+                      float* d_target_image, const float* d_image, int64_t n_image, void* stream);
+
 const char* pbn_last_error(void);
 int pbn_abi_version(void);
 

@@ -25,6 +25,8 @@
 //   ddqn_adam    every block adds the blocks' sums in the same fixed order (the total norm of
 //                clip_grad_norm_), scales the gradient and takes the Adam step.
 //   dqn_pack     again, on the new weights: the online image.
+//   ddqn_schedule  a captured frame's _schedule_step: beta's increment and, on the frames where it is
+//                due, the hard target copy (parameters and image), decided on the device.
 //
 // Every reduction runs in a fixed order and nothing is accumulated with atomics: two runs from the
 // same state give the same bits.
@@ -665,7 +667,51 @@ __global__ void __launch_bounds__(kGradThreads) ddqn_adam_kernel(LearnArgs a) {
   }
 }
 
+// ---- the schedule step ---------------------------------------------------------------------------
+// _schedule_step's beta and hard target copy (ddqn_per/__init__.py:283-290, :488-490) for a frame
+// that is replayed from a graph: beta moves in place, and the copy is due when the frames done so
+// far, *step - base, are a multiple of `every`.  *step is the env step index that an EARLIER launch
+// of the frame advanced (pbn_replay_advance) and nothing here writes, so every block reads the same
+// value and takes the same branch; only thread 0 of block 0 touches *beta, which no other thread
+// reads.  Not due: a block leaves after that one load.  Due: both ranges as one run of 16-byte
+// vectors, grid-stride, plain loads and stores (the target image is read by the next update).
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+struct ScheduleArgs {
+  double* beta;
+  double beta_inc;
+  const int64_t* step;
+  int64_t base, every;
+  u32x4* t_flat;
+  const u32x4* q_flat;
+  int64_t n_flat;   // 16-byte vectors
+  u32x4* t_img;
+  const u32x4* q_img;
+  int64_t n_img;
+};
+
+__global__ void __launch_bounds__(256) ddqn_schedule_kernel(ScheduleArgs a) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const double b = *a.beta + a.beta_inc;
+    *a.beta = b > 1.0 ? 1.0 : b;   // min(beta + increment, 1)
+  }
+  if ((*a.step - a.base) % a.every != 0) return;
+  const int64_t n = a.n_flat + a.n_img, stride = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    if (i < a.n_flat)
+      a.t_flat[i] = a.q_flat[i];
+    else
+      a.t_img[i - a.n_flat] = a.q_img[i - a.n_flat];
+  }
+}
+
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+bool overlap(const void* p, const void* q, int64_t bytes) {
+  const char* a = static_cast<const char*>(p);
+  const char* b = static_cast<const char*>(q);
+  return a < b + bytes && b < a + bytes;
+}
 
 int check_batch(int64_t batch) {
   if (batch < 16 || batch > 1024 || (batch & 15))
@@ -842,6 +888,40 @@ int pbn_ddqn_learn(const pbn_net* net, int32_t h0, int32_t h1, int64_t batch, co
   if (hipGetLastError() != hipSuccess) return pbn::set_error(PBN_EDEVICE, "ddqn_adam_kernel launch failed");
   hipLaunchKernelGGL(dqn_pack_kernel, dim3(pack_blocks(a.d)), dim3(256), 0, s, a.d, d_params, nv.att_first, d_image);
   if (hipGetLastError() != hipSuccess) return pbn::set_error(PBN_EDEVICE, "dqn_pack_kernel launch failed");
+  return PBN_OK;
+}
+
+int pbn_ddqn_schedule(double* d_beta, double beta_increment, const int64_t* d_step, int64_t step_base,
+                      int64_t target_update, float* d_target_params, const float* d_params, int64_t n_params,
+                      float* d_target_image, const float* d_image, int64_t n_image, void* stream) {
+  if (!d_beta || !d_step) return pbn::set_error(PBN_EINVAL, "pbn_ddqn_schedule: null d_beta or d_step");
+  if (((uintptr_t)d_beta | (uintptr_t)d_step) & 7u)
+    return pbn::set_error(PBN_EINVAL, "pbn_ddqn_schedule: d_beta and d_step must be 8-byte aligned");
+  if (target_update < 1) return pbn::set_error(PBN_EINVAL, "pbn_ddqn_schedule: target_update >= 1");
+  if (n_params < 4 || n_image < 4 || (n_params & 3) || (n_image & 3))
+    return pbn::set_error(PBN_EINVAL, "pbn_ddqn_schedule: n_params and n_image must be positive multiples of 4");
+  if (!d_target_params || !d_params || !d_target_image || !d_image)
+    return pbn::set_error(PBN_EINVAL, "pbn_ddqn_schedule: null buffer");
+  if (!aligned16(d_target_params) || !aligned16(d_params) || !aligned16(d_target_image) || !aligned16(d_image))
+    return pbn::set_error(PBN_EINVAL, "pbn_ddqn_schedule: parameter and image buffers: 16-byte aligned");
+  if (overlap(d_target_params, d_params, n_params * 4) || overlap(d_target_image, d_image, n_image * 4))
+    return pbn::set_error(PBN_EINVAL, "pbn_ddqn_schedule: a target buffer overlaps its source");
+  ScheduleArgs a;
+  a.beta = d_beta;
+  a.beta_inc = beta_increment;
+  a.step = d_step;
+  a.base = step_base;
+  a.every = target_update;
+  a.t_flat = reinterpret_cast<u32x4*>(d_target_params);
+  a.q_flat = reinterpret_cast<const u32x4*>(d_params);
+  a.n_flat = n_params / 4;
+  a.t_img = reinterpret_cast<u32x4*>(d_target_image);
+  a.q_img = reinterpret_cast<const u32x4*>(d_image);
+  a.n_img = n_image / 4;
+  // one vector per thread up to 1,024 blocks (a few hundred KB: some tens), grid-stride past that
+  const unsigned blocks = (unsigned)std::min<int64_t>((a.n_flat + a.n_img + 255) / 256, 1024);
+  hipLaunchKernelGGL(ddqn_schedule_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+  if (hipGetLastError() != hipSuccess) return pbn::set_error(PBN_EDEVICE, "ddqn_schedule_kernel launch failed");
   return PBN_OK;
 }
 

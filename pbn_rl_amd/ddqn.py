@@ -12,6 +12,7 @@ double-DQN / Huber / clip_grad_norm_ / Adam step.  Here one frame covers a whole
     pbn_replay_store             the transitions into the device ring               (HIP)
     pbn_per_sample / _update     prioritised replay (replay.py, csrc/pbn_per.hip)   (HIP)
     pbn_ddqn_learn               _learn_step on a flat parameter buffer, 4 launches (HIP, MFMA)
+    pbn_ddqn_schedule            a captured frame's beta step and due target copy   (HIP)
 
 ``DQN`` keeps ddqn_per/network.py's module tree and parameter names, so the ``"params"`` entry of
 a reference ``ddqn_*.pt`` loads with ``load_state_dict``.  ``ddqn_update`` restates ``_get_loss`` +
@@ -453,7 +454,12 @@ class DDQNLearner:
     with importance weights -> update_priorities with |w_b h_b| + ``replay_constant``.
     ``fused`` (default: when ``ddqn_fused_supported`` and the env is on the GPU) runs acting and the
     update as the HIP launches of csrc/pbn_ddqn.hip; ``fused=False`` acts through ``DQN.forward``
-    and updates with ``ddqn_update`` + torch.optim.Adam."""
+    and updates with ``ddqn_update`` + torch.optim.Adam.
+
+    ``graphable=True`` allows ``capture()``: the fused, prioritised frame (``train_frequency`` 1) as
+    one hipGraph, every counter and both schedules in device memory, the target copy decided on the
+    device (pbn_ddqn_schedule).  ``frame()`` then replays it, and ``run(k)`` replays it ``k`` times
+    with no host work between the replays.  Without ``capture()`` the frames are the eager ones."""
 
     def __init__(self, env, dqn: Optional[DQN] = None, *, net_arch=((50, 50),), total_frames: int,
                  capacity: int, batch_size: int = 64, target_update: int = 512, gamma: float = 0.95,
@@ -461,7 +467,7 @@ class DDQNLearner:
                  learning_rate: float = 1e-4, max_grad_norm: float = 10.0, learning_starts: int = 0,
                  train_frequency: int = 1, prioritised: bool = True, per_alpha: float = 0.6, per_beta: float = 0.4,
                  per_max_beta: float = 1.0, beta_fraction: float = 0.75, replay_constant: float = 1e-5,
-                 fused: Optional[bool] = None, seed: int = 0):
+                 fused: Optional[bool] = None, seed: int = 0, graphable: bool = False):
         dev = torch.device(env.device)
         on_gpu = dev.type == "cuda"
         if prioritised and not on_gpu:
@@ -516,6 +522,9 @@ class DDQNLearner:
         self.syncs: List[int] = []          # the frames whose schedule step copied the target
         self.last_loss: Optional[torch.Tensor] = None
         self.last_beta: Optional[float] = None   # the beta of the last prioritised sample
+        self.per_max_beta = float(per_max_beta)
+        self.graphable = bool(graphable)
+        self._graph: Optional[torch.cuda.CUDAGraph] = None
 
     def gather(self, idx: torch.Tensor) -> Dict[str, torch.Tensor]:
         """Rows ``idx`` of the ring as ``ddqn_update``'s batch (pbn_replay_batch when it takes the
@@ -558,6 +567,8 @@ class DDQNLearner:
     def frame(self):
         """One global_step for every env; returns (reward, done) of the ``num_envs`` envs, ``done``
         = terminated or truncated (the episode ended; what is stored is terminated alone)."""
+        if self._graph is not None:
+            return self.run(1)
         env, rp = self.env, self.replay
         f = self.frames
         state = env.state.clone()
@@ -580,6 +591,154 @@ class DDQNLearner:
         self.frames = f + 1
         done = (flags & (_lib.FLAG_TERMINATED | _lib.FLAG_TRUNCATED)) != 0
         return reward, done
+
+    # ---- graph-captured frames -------------------------------------------------------------
+    def _check_capturable(self) -> None:
+        """capture()'s refusals; nothing here touches the GPU."""
+        if not self.graphable:
+            raise ValueError("construct the learner with graphable=True to capture it")
+        wrong = []
+        if self.fused is None:
+            wrong.append("fused: the captured frame runs the HIP update (fused=True), not the PyTorch one")
+        if not self.prioritised:
+            wrong.append("prioritised: the captured frame samples from prioritised replay (prioritised=True)")
+        if self.train_frequency != 1:
+            wrong.append(f"train_frequency: the captured frame updates every frame (1), not every {self.train_frequency}")
+        if self.per_max_beta < 1.0:
+            wrong.append("per_max_beta: the captured schedule moves replay.beta_t itself, which every sample clamps "
+                         "to per_max_beta; it must be >= 1")
+        if wrong:
+            raise ValueError("capture() cannot take this learner -- " + "; ".join(wrong))
+
+    def capture(self, min_updates: int = 1) -> None:
+        """Capture one whole learning frame in a hipGraph; ``frame()`` replays it from then on and
+        ``run(k)`` replays it ``k`` times back to back.  The frame is one chain of launches:
+
+            pbn_dqn_flipmask_from_state  act at *step and *epsilon
+            pbn_step_dev_store           the step, writing its transitions into the ring (settle law:
+                                         pbn_step_dev, then pbn_replay_store, which also moves the
+                                         stepped state into ``env.state``)
+            pbn_per_store                the new rows' priorities
+            pbn_replay_advance           ring position, fill level, step index, epsilon's decay
+            pbn_per_sample               over the fill level the store left, at *beta
+            pbn_ddqn_learn               weights in, priorities out
+            pbn_per_update
+            pbn_ddqn_schedule            beta's increment and, when due, the hard target copy
+
+        The step index, epsilon, beta, the ring position and fill level, the draw counter and Adam's
+        step count live in device memory; the host mirrors them after the replays with the eager
+        frame's own arithmetic.  Frames run eagerly (on a side stream, as capture requires) until
+        every later frame learns and ``min_updates`` updates are done.  Fused and prioritised with
+        ``train_frequency`` 1 only; after capture the env must only be stepped through ``frame()`` /
+        ``run()``.  Weights loaded between replays are repacked by the next replay (``sync()``)."""
+        self._check_capturable()
+        if self._graph is not None:
+            raise ValueError("the frame is already captured")
+        env, rp, dev = self.env, self.replay, torch.device(self.env.device)
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            while (self.frames <= self.learning_starts or rp.size < max(self.batch_size, 2)
+                   or self.updates < min_updates):
+                self.frame()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        self._step_t = torch.full((1,), env.step_index, dtype=torch.int64, device=dev)
+        self._step_base = env.step_index - self.frames      # *step - base = the frames done
+        self._eps64 = torch.full((1,), self.epsilon, dtype=torch.float64, device=dev)
+        self._eps32 = self._eps64.float()     # (the eager frame's c_float of the same double: one rounding)
+        rp.beta_t.fill_(self.beta)            # the next frame's beta; the schedule launch moves it from here on
+        self._ring = self._tgt_prev = None
+        if env.spec.settle < 2:
+            # one-update law: the step kernel writes the ring rows itself (pbn_step_dev_store)
+            self._ring = _lib.RingStore(
+                rp.capacity, self._pos_t.data_ptr(), rp.state.data_ptr(), rp.next_state.data_ptr(),
+                rp.target.data_ptr(), rp.action.data_ptr(), rp.reward.data_ptr(), rp.done.data_ptr(),
+                self.agent.actions.data_ptr(), 1, _lib.FLAG_TERMINATED, None)
+        else:
+            self._tgt_prev = env.target.clone()   # the pre-step targets, carried by the ring store
+        self.fused.sync()                         # (a repack belongs before the capture, not in it)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._graph_body()
+        self._graph = g
+        # the capture recorded the frame without running it: nothing above advanced
+        torch.cuda.current_stream(dev).synchronize()
+
+    def _graph_body(self) -> None:
+        env, rp, fu = self.env, self.replay, self.fused
+        self.agent.act_q(step_t=self._step_t, epsilon_t=self._eps32)
+        if self._ring is not None:
+            env.step_flipmask_dev_store(self._step_t, self._ring)
+            rp.store_priorities(env.n_alloc, self._pos_t)
+        else:
+            env.step_flipmask_dev(self._step_t, copy_back=False)
+            # the ring store reads the pre-step state (still in env.state) and target (carried in
+            # _tgt_prev) and in the same pass moves the stepped state into env.state and the new
+            # targets into _tgt_prev; PrioritisedDeviceReplay.store_at stores the priorities first
+            rp.store_at(self._pos_t, self._size_t, env.state, self._tgt_prev, self.agent.actions.view(-1, 1),
+                        env.reward, env.final_state, env.flags, done_mask=_lib.FLAG_TERMINATED, advance=False,
+                        state_copy=(env.state, env._state_next), target_copy=(self._tgt_prev, env.target))
+        # the counters before the sample: it must see the fill level the store left, as the eager
+        # frame's does
+        L = _lib.load()
+        with torch.cuda.device(env.device):
+            _lib.check(L.pbn_replay_advance(env.n_alloc, rp.capacity, self._pos_t.data_ptr(), self._size_t.data_ptr(),
+                                            self._step_t.data_ptr(), self._eps64.data_ptr(), self._eps32.data_ptr(),
+                                            float(self.min_epsilon), float(self.epsilon_decrement), 0, 0, None, None,
+                                            env._stream()), "pbn_replay_advance")
+        self._g_idx, self._g_w = rp.sample(self.batch_size, size_t=self._size_t)
+        fu.update(rp, self._g_idx, weights=self._g_w, priorities_out=self._prio,
+                  replay_constant=self.replay_constant)
+        rp.update_priorities(self._g_idx, self._prio, self._size_t)
+        with torch.cuda.device(env.device):
+            _lib.check(L.pbn_ddqn_schedule(rp.beta_t.data_ptr(), float(self.beta_increment), self._step_t.data_ptr(),
+                                           self._step_base, self.target_update, fu.t_flat.data_ptr(),
+                                           fu.q_flat.data_ptr(), fu.q_flat.numel(), fu.t_image.data_ptr(),
+                                           fu.q_image.data_ptr(), fu.q_image.numel(), env._stream()),
+                       "pbn_ddqn_schedule")
+
+    def _mirror(self, k: int) -> None:
+        """The host's copies after ``k`` replays: the eager frame's own arithmetic, ``k`` times."""
+        env, rp, fu = self.env, self.replay, self.fused
+        synced = False
+        for _ in range(k):
+            f = self.frames
+            env.step_index += 1
+            rp.pos = (rp.pos + env.n_alloc) % rp.capacity
+            rp.size = min(rp.size + env.n_alloc, rp.capacity)
+            rp.beta = self.last_beta = self.beta     # the beta this frame's sample read
+            rp.mirror_beta()
+            self.updates += 1
+            self.epsilon = max(self.min_epsilon, self.epsilon - self.epsilon_decrement)
+            if (f + 1) % self.target_update == 0:
+                self.syncs.append(f)
+                synced = True
+            self.beta = min(self.beta + self.beta_increment, 1)
+            self.frames = f + 1
+        # the replays rewrote the online parameters in place, and the target's on sync frames (the
+        # version counters are what sync(), BatchedDDQN and PyTorch read)
+        fu.mark_updated()
+        if synced:
+            fu._bump(fu._tp)
+            fu._tv = fu._versions(fu._tp)
+        self.last_loss = fu.loss[0]
+
+    def run(self, k: int):
+        """``k`` captured frames replayed back to back, nothing on the host between them; then the
+        host's copies move to their values after ``k`` frames.  Returns the last frame's (reward,
+        done), as ``frame()`` does."""
+        if self._graph is None:
+            raise ValueError("run() replays the captured frame: call capture() first")
+        if k < 1:
+            raise ValueError("k must be >= 1")
+        self.fused.sync()                # weights loaded since the last replay: repack their images
+        for _ in range(k):
+            self._graph.replay()
+        self._mirror(k)
+        env = self.env
+        n = env.num_envs
+        done = (env.flags[:n] & (_lib.FLAG_TERMINATED | _lib.FLAG_TRUNCATED)) != 0
+        return env.reward[:n], done
 
 
 def load_ddqn_checkpoint(path: str) -> DQN:

@@ -8,11 +8,16 @@ pbn_q_to_flipmask, the update through ddqn_update + torch.optim.Adam).
       update  HIP-event time of one update on the same ring rows: FusedDDQNUpdate.update (4 launches)
               beside gather + ddqn_update, each unweighted and with importance weights
       frame   one whole DDQNLearner.frame(), prioritised and uniform, both paths: alternating runs of
-              ``--frames-per-run`` frames, whole-run host time ending in a device synchronise
+              ``--frames-per-run`` frames, whole-run host time ending in a device synchronise; and the
+              prioritised HIP frame captured in one hipGraph (DDQNLearner.capture), timed the same
+              way: "captured" replays once per frame(), "captured run" is one run(k) per run
     ``reps`` calls are timed one by one between a pair of events after a warm-up, the legs in
     alternating blocks; the median and the spread are reported.
   rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o run -- python tools/ddqn_bench.py --no-frames
       then ``--trace DIR`` on a later run adds the trace's per-kernel times of the new kernels.
+  rocprofv3 --kernel-trace --stats --output-format csv -d DIR2 -o run -- python tools/ddqn_bench.py --captured-frames 200
+      then ``--frame-trace DIR2`` adds the captured frame's launch list with each kernel's median
+      time and their sum over one frame.
 
 The result is one JSON line (and ``--out``)."""
 import argparse
@@ -127,32 +132,53 @@ def bench_update(args):
     return alternate(legs, args.reps)
 
 
-def run_frames(lr, frames):
+def run_frames(lr, frames, run_k=False):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(frames):
-        lr.frame()
+    if run_k:
+        lr.run(frames)
+    else:
+        for _ in range(frames):
+            lr.frame()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / frames * 1e6
 
 
+CAPTURED, CAPTURED_RUN = "prioritised hip captured", "prioritised hip captured run"
+
+
 def bench_frames(args):
     lrs = {}
+
+    def learner(prioritised, fused, **kw):
+        env = VectorPBNEnv(spec28(), args.envs, seed=3)
+        torch.manual_seed(0)
+        lr = DDQNLearner(env, DQN(28, 29, ARCH), total_frames=10 ** 6, capacity=args.capacity,
+                         batch_size=args.batch, prioritised=prioritised, fused=fused, seed=5, **kw)
+        env.reset()
+        return lr
+
     for prioritised in (True, False):
         for fused in (True, False):
-            env = VectorPBNEnv(spec28(), args.envs, seed=3)
-            torch.manual_seed(0)
-            lr = DDQNLearner(env, DQN(28, 29, ARCH), total_frames=10 ** 6, capacity=args.capacity,
-                             batch_size=args.batch, prioritised=prioritised, fused=fused, seed=5)
-            env.reset()
+            lr = learner(prioritised, fused)
             run_frames(lr, 8)
             lrs[("prioritised" if prioritised else "uniform") + (" hip" if fused else " pytorch")] = lr
+    # the same frame captured in one hipGraph: one replay per frame(), and run(k)'s back-to-back replays
+    for name in (CAPTURED, CAPTURED_RUN):
+        lr = learner(True, True, graphable=True)
+        lr.capture()
+        run_frames(lr, 8, run_k=name == CAPTURED_RUN)
+        lrs[name] = lr
     samples = {k: [] for k in lrs}
     for _ in range(args.reps_frames):              # alternating
         for k, lr in lrs.items():
-            samples[k].append(run_frames(lr, args.frames))
-    return {k: {"median_us_per_frame": statistics.median(v), "min_us": min(v), "max_us": max(v), "samples_us": v}
-            for k, v in samples.items()}
+            samples[k].append(run_frames(lr, args.frames, run_k=k == CAPTURED_RUN))
+    out = {k: {"median_us_per_frame": statistics.median(v), "min_us": min(v), "max_us": max(v), "samples_us": v}
+           for k, v in samples.items()}
+    eager = out["prioritised hip"]["median_us_per_frame"]
+    for name in (CAPTURED, CAPTURED_RUN):
+        out[name]["ratio_to_prioritised_hip"] = out[name]["median_us_per_frame"] / eager
+    return out
 
 
 def trace_averages(trace_dir):
@@ -171,8 +197,48 @@ def trace_averages(trace_dir):
             for k, v in acc.items()}
 
 
+def captured_frames_only(args):
+    """The process to put under rocprofv3 --kernel-trace for the captured frame: capture, then
+    ``--captured-frames`` replays through run(k), and nothing else."""
+    env = VectorPBNEnv(spec28(), args.envs, seed=3)
+    torch.manual_seed(0)
+    lr = DDQNLearner(env, DQN(28, 29, ARCH), total_frames=10 ** 6, capacity=args.capacity, batch_size=args.batch,
+                     prioritised=True, fused=True, seed=5, graphable=True)
+    env.reset()
+    lr.capture()
+    lr.run(args.captured_frames)
+    torch.cuda.synchronize()
+    print(json.dumps({"captured_frames": args.captured_frames, "frames": lr.frames, "updates": lr.updates}), flush=True)
+
+
+def frame_trace(trace_dir, frames):
+    """The captured frame's kernels from the kernel-trace csv of a ``--captured-frames frames`` run:
+    every kernel dispatched at least once per replayed frame (the few eager frames before the
+    capture and the set-up dispatch the rest), its dispatches per frame, its median time, and the sum
+    over one frame."""
+    files = glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True)
+    if not files:
+        raise SystemExit(f"no *kernel_trace.csv under {trace_dir}")
+    acc = {}
+    for path in files:
+        with open(path, newline="") as f:
+            for row in csv.DictReader(f):
+                name = row["Kernel_Name"].replace("(anonymous namespace)::", "").split("(")[0].strip()
+                acc.setdefault(name, []).append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3)
+    kernels = {k: {"per_frame": len(v) // frames, "median_us": statistics.median(v), "dispatches": len(v)}
+               for k, v in acc.items() if len(v) >= frames}
+    return {"frames": frames, "kernels": kernels,
+            "launches_per_frame": sum(k["per_frame"] for k in kernels.values()),
+            "sum_us_per_frame": sum(k["per_frame"] * k["median_us"] for k in kernels.values())}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--captured-frames", type=int, default=0,
+                    help="only capture the prioritised frame and replay it this many times (for rocprofv3)")
+    ap.add_argument("--frame-trace", default=None,
+                    help="directory of a rocprofv3 --kernel-trace run of --captured-frames (with --frame-trace-frames)")
+    ap.add_argument("--frame-trace-frames", type=int, default=200)
     ap.add_argument("--no-frames", action="store_true", help="the acting and update legs only")
     ap.add_argument("--trace", default=None, help="directory of a rocprofv3 --kernel-trace run")
     ap.add_argument("--envs", type=int, default=32768)
@@ -185,10 +251,14 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("ddqn_bench needs a GPU")
+    if args.captured_frames:
+        return captured_frames_only(args)
     res = {"what": f"DDQN / DDQNPER, pbn28, DQN(28, 29, {ARCH}), {args.envs} envs, capacity {args.capacity}, "
                    f"batch {args.batch}", "device": torch.cuda.get_device_name(0)}
     if args.trace:
         res["kernel_trace"] = trace_averages(args.trace)
+    if args.frame_trace:
+        res["captured_frame_kernel_trace"] = frame_trace(args.frame_trace, args.frame_trace_frames)
     res["act_hip_events"] = bench_act(args)
     res["update_hip_events"] = bench_update(args)
     if not args.no_frames:
