@@ -17,7 +17,9 @@ double-DQN / Huber / clip_grad_norm_ / Adam step.  Here one frame covers a whole
 ``DQN`` keeps ddqn_per/network.py's module tree and parameter names, so the ``"params"`` entry of
 a reference ``ddqn_*.pt`` loads with ``load_state_dict``.  ``ddqn_update`` restates ``_get_loss`` +
 ``_back_propagate`` (with weights: ``DDQNPER._learn_step``) in PyTorch: the ``fused=False`` path
-and what tests/golden/ddqn_update.npz pins.
+and what tests/golden/ddqn_update.npz pins.  ``FusedDDQNUpdate`` keeps its buffers as fused.py's
+FusedUpdate does, and ``DDQNLearner``'s captured frame is built from learner.py's FrameLearner, as
+the BDQ agent's are (replay.py).
 """
 from __future__ import annotations
 
@@ -30,7 +32,10 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from .replay import DeviceReplay, FusedBDQUpdate, PrioritisedDeviceReplay
+from .fused import FusedUpdate
+from .learner import FrameLearner
+from .replay import DeviceReplay, PrioritisedDeviceReplay
+from .vector_env import unpack_states
 
 __all__ = ["DQN", "ddqn_update", "BatchedDDQN", "FusedDDQNUpdate", "ddqn_fused_supported", "DDQNLearner",
            "dqn_layout", "load_ddqn_checkpoint"]
@@ -142,9 +147,7 @@ def _first_states(spec, device) -> torch.Tensor:
 
 def _unpack(words: torch.Tensor, n_nodes: int) -> torch.Tensor:
     """Packed state words (W, B) int32 -> (B, N) float32 (bit i of word w = node 32 w + i)."""
-    sh = torch.arange(32, device=words.device, dtype=torch.int32)
-    bits = (words.t().unsqueeze(2) >> sh) & 1
-    return bits.reshape(words.shape[1], -1)[:, :n_nodes].to(torch.float32)
+    return unpack_states(words, n_nodes).to(torch.float32)
 
 
 class BatchedDDQN:
@@ -292,97 +295,48 @@ class BatchedDDQN:
         return self.env.step_flipmask(use_current=True)
 
 
-class FusedDDQNUpdate:
+class FusedDDQNUpdate(FusedUpdate):
     """``_learn_step`` (ddqn_per/__init__.py:275-278, :468-483) as pbn_ddqn_learn's four HIP launches
     instead of PyTorch's forward / autograd / clip / Adam kernels.
 
-    The online network's parameters move into one flat fp32 buffer (``pbn_dqn_layout``) and become
-    views of it, and so do the target's; ``state_dict``, the PyTorch forward and the kernels see the
-    same weights.  Each network has an image (``q_image`` / ``t_image``, pbn_dqn_pack): the bilinear
-    layer contracted with every attractor's first state, the padded biases and the dense weights
-    as MFMA-fragment tiles.  Every update rewrites the online image; ``pack()`` rebuilds the images
-    after weights change any other way (a loaded checkpoint); ``sync_target()`` is the hard target
-    copy (:286-287), parameters and image, device to device.  Adam (torch.optim.Adam's arithmetic)
-    keeps its moments in buffers of the same layout and its step count on the device."""
+    The buffers and their bookkeeping are FusedUpdate's (fused.py); the flat layout is
+    ``pbn_dqn_layout``.  A network's image (pbn_dqn_pack) is the bilinear layer contracted with every
+    attractor's first state, the padded biases and the dense weights as MFMA-fragment tiles.  Every
+    update rewrites the online image; ``pack()`` rebuilds the images after weights change any other
+    way (a loaded checkpoint); ``sync_target()`` is the hard target copy (:286-287), parameters and
+    image, device to device.  Adam is torch.optim.Adam's arithmetic."""
 
     def __init__(self, q: DQN, target: DQN, net, *, batch_size: int, learning_rate: float = 1e-4,
                  gamma: float = 0.95, max_grad_norm: float = 10.0, betas=(0.9, 0.999), eps: float = 1e-8,
                  keep_grad: bool = False):
         N = net.spec.n
-        dev = next(q.parameters()).device
-        if dev.type != "cuda":
-            raise ValueError("FusedDDQNUpdate runs on the GPU")
+        self._require_gpu(q)
         self.h0, self.h1 = _check_dqn(q, N)
         if _check_dqn(target, N) != (self.h0, self.h1):
             raise ValueError("the target network must have the online network's shape")
         if not ddqn_fused_supported(N, [(self.h0, self.h1)], batch_size):
             raise ValueError("pbn_ddqn_learn: one hidden Linear, widths <= 64, N + 1 <= 128, batch a multiple "
                              "of 16 and <= 1024")
-        self.net, self.N, self.B = net, N, int(batch_size)
-        self.lr, self.gamma, self.max_grad_norm = float(learning_rate), float(gamma), float(max_grad_norm)
-        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        self.max_grad_norm = float(max_grad_norm)
         self.off = dqn_layout(N, self.h0, self.h1)
-        self.q, self.target = q, target
-        self.q_flat = self._flatten(q, dev)
-        self.t_flat = self._flatten(target, dev)
-        self._qp, self._tp = _segments(q), _segments(target)
-        self._qv = self._tv = None
-        self.m = torch.zeros_like(self.q_flat)
-        self.v = torch.zeros_like(self.q_flat)
-        self.step = torch.zeros(1, dtype=torch.float32, device=dev)
+        super().__init__(q, target, net, batch_size=batch_size, learning_rate=learning_rate, gamma=gamma, betas=betas,
+                         eps=eps, keep_grad=keep_grad)
+        self.grad_norm = torch.zeros(1, dtype=torch.float32, device=self.q_flat.device)
+
+    def _sizes(self):
         L = _lib.load()
         nimg, nbytes = ctypes.c_int64(), ctypes.c_int64()
-        _lib.check(L.pbn_dqn_image_floats(net.handle, self.h0, self.h1, ctypes.byref(nimg)), "pbn_dqn_image_floats")
-        self.q_image = torch.zeros(nimg.value, dtype=torch.float32, device=dev)
-        self.t_image = torch.zeros_like(self.q_image)
-        _lib.check(L.pbn_ddqn_learn_workspace(N, self.h0, self.h1, self.B, ctypes.byref(nbytes)),
+        _lib.check(L.pbn_dqn_image_floats(self.net.handle, self.h0, self.h1, ctypes.byref(nimg)), "pbn_dqn_image_floats")
+        _lib.check(L.pbn_ddqn_learn_workspace(self.N, self.h0, self.h1, self.B, ctypes.byref(nbytes)),
                    "pbn_ddqn_learn_workspace")
-        self.work = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=dev)
-        self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.grad_norm = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.grad = torch.zeros_like(self.q_flat) if keep_grad else None
-        self.pack()
+        return self.off[6], nimg.value, nbytes.value
 
-    def _flatten(self, q: DQN, dev) -> torch.Tensor:
-        flat = torch.zeros(self.off[6], dtype=torch.float32, device=dev)
-        with torch.no_grad():
-            for p, at in zip(_segments(q), self.off):
-                view = flat[at:at + p.numel()].view(p.shape)
-                view.copy_(p.detach())
-                p.data = view
-        return flat
+    def _params(self, q: DQN):
+        return list(zip(_segments(q), self.off))
 
-    def _stream(self):
-        return torch.cuda.current_stream(self.q_flat.device).cuda_stream
-
-    _versions = staticmethod(FusedBDQUpdate._versions)
-    _bump = staticmethod(FusedBDQUpdate._bump)
-
-    def pack(self, which: str = "both") -> None:
-        """Recompute the image (pbn_dqn_pack) of the online and/or target network."""
-        L = _lib.load()
-        with torch.cuda.device(self.q_flat.device):
-            for name, flat, image in (("online", self.q_flat, self.q_image), ("target", self.t_flat, self.t_image)):
-                if which in ("both", name):
-                    _lib.check(L.pbn_dqn_pack(self.net.handle, self.h0, self.h1, flat.data_ptr(), image.data_ptr(),
-                                              self._stream()), "pbn_dqn_pack")
-        if which in ("both", "online"):
-            self._qv = self._versions(self._qp)
-        if which in ("both", "target"):
-            self._tv = self._versions(self._tp)
-
-    def sync(self) -> None:
-        """Repack the image of a network whose parameters changed since its last pack (e.g. a
-        load_state_dict); a no-op otherwise."""
-        if self._versions(self._qp) != self._qv:
-            self.pack("online")
-        if self._versions(self._tp) != self._tv:
-            self.pack("target")
-
-    def mark_updated(self) -> None:
-        """After a pbn_ddqn_learn launch: the online parameters changed in place."""
-        self._bump(self._qp)
-        self._qv = self._versions(self._qp)
+    def _pack(self, flat: torch.Tensor, image: torch.Tensor) -> None:
+        _lib.check(_lib.load().pbn_dqn_pack(self.net.handle, self.h0, self.h1, flat.data_ptr(), image.data_ptr(),
+                                            self._stream()), "pbn_dqn_pack")
 
     def sync_target(self) -> None:
         """target <- online (``self.target.load_state_dict(self.controller.state_dict())``,
@@ -394,8 +348,7 @@ class FusedDDQNUpdate:
                                         self._stream()), "pbn_copy_async")
             _lib.check(L.pbn_copy_async(self.t_image.data_ptr(), self.q_image.data_ptr(), self.q_image.numel() * 4,
                                         self._stream()), "pbn_copy_async")
-        self._bump(self._tp)
-        self._tv = self._versions(self._tp)
+        self.mark_target_updated()
 
     def acting_image(self) -> torch.Tensor:
         """BatchedDDQN's image provider: the online image, repacked first if the weights were
@@ -409,11 +362,10 @@ class FusedDDQNUpdate:
         element (overwritten by the next update; ``grad_norm`` holds the total norm before
         clipping).  ``weights`` / ``priorities_out`` (float32 [B] on the device, both or neither):
         DDQNPER's importance weights by batch position in, |w_b h_b| + ``replay_constant`` out."""
-        if idx.shape != (self.B,) or idx.dtype != torch.int64:
-            raise ValueError(f"idx must be {self.B} int64 ring indices")
+        self._check_idx(idx)
         if replay.action.shape[1] != 1:
             raise ValueError("the replay ring must hold one action per transition")
-        FusedBDQUpdate.check_per_args(self.B, self.q_flat.device, weights, priorities_out)
+        self.check_per_args(self.B, self.q_flat.device, weights, priorities_out)
         self.sync()
         b1, b2 = self.betas
         with torch.cuda.device(self.q_flat.device):
@@ -431,15 +383,8 @@ class FusedDDQNUpdate:
             self.mark_updated()
         return self.loss[0]
 
-    def grads(self) -> List[torch.Tensor]:
-        """The last update's clipped gradient (keep_grad=True) as views shaped like q.parameters()."""
-        if self.grad is None:
-            raise ValueError("construct with keep_grad=True")
-        g = {id(p): self.grad[at:at + p.numel()].view(p.shape) for p, at in zip(self._qp, self.off)}
-        return [g[id(p)] for p in self.q.parameters()]
 
-
-class DDQNLearner:
+class DDQNLearner(FrameLearner):
     """``DDQN.learn`` / ``DDQNPER`` (ddqn_per/__init__.py:308-403, :431-539) over a VectorPBNEnv; the
     defaults are train_ddqn.py's.  One ``frame()`` is one reference ``global_step`` for every env:
     act at the current epsilon, step, store all ``n_alloc`` transitions with ``done`` = TERMINATED
@@ -635,27 +580,12 @@ class DDQNLearner:
         if self._graph is not None:
             raise ValueError("the frame is already captured")
         env, rp, dev = self.env, self.replay, torch.device(self.env.device)
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            while (self.frames <= self.learning_starts or rp.size < max(self.batch_size, 2)
-                   or self.updates < min_updates):
-                self.frame()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        self._step_t = torch.full((1,), env.step_index, dtype=torch.int64, device=dev)
+        self._warm_up(lambda: (self.frames > self.learning_starts and rp.size >= max(self.batch_size, 2)
+                               and self.updates >= min_updates))
+        self._capture_counters(self.min_epsilon, self.epsilon_decrement, 0)
         self._step_base = env.step_index - self.frames      # *step - base = the frames done
-        self._eps64 = torch.full((1,), self.epsilon, dtype=torch.float64, device=dev)
-        self._eps32 = self._eps64.float()     # (the eager frame's c_float of the same double: one rounding)
         rp.beta_t.fill_(self.beta)            # the next frame's beta; the schedule launch moves it from here on
-        self._ring = self._tgt_prev = None
-        if env.spec.settle < 2:
-            # one-update law: the step kernel writes the ring rows itself (pbn_step_dev_store)
-            self._ring = _lib.RingStore(
-                rp.capacity, self._pos_t.data_ptr(), rp.state.data_ptr(), rp.next_state.data_ptr(),
-                rp.target.data_ptr(), rp.action.data_ptr(), rp.reward.data_ptr(), rp.done.data_ptr(),
-                self.agent.actions.data_ptr(), 1, _lib.FLAG_TERMINATED, None)
-        else:
-            self._tgt_prev = env.target.clone()   # the pre-step targets, carried by the ring store
+        self._capture_ring(_lib.FLAG_TERMINATED, None, self.agent.actions.view(-1, 1))
         self.fused.sync()                         # (a repack belongs before the capture, not in it)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
@@ -667,49 +597,30 @@ class DDQNLearner:
     def _graph_body(self) -> None:
         env, rp, fu = self.env, self.replay, self.fused
         self.agent.act_q(step_t=self._step_t, epsilon_t=self._eps32)
-        if self._ring is not None:
-            env.step_flipmask_dev_store(self._step_t, self._ring)
-            rp.store_priorities(env.n_alloc, self._pos_t)
-        else:
-            env.step_flipmask_dev(self._step_t, copy_back=False)
-            # the ring store reads the pre-step state (still in env.state) and target (carried in
-            # _tgt_prev) and in the same pass moves the stepped state into env.state and the new
-            # targets into _tgt_prev; PrioritisedDeviceReplay.store_at stores the priorities first
-            rp.store_at(self._pos_t, self._size_t, env.state, self._tgt_prev, self.agent.actions.view(-1, 1),
-                        env.reward, env.final_state, env.flags, done_mask=_lib.FLAG_TERMINATED, advance=False,
-                        state_copy=(env.state, env._state_next), target_copy=(self._tgt_prev, env.target))
+        self._step_and_store()
         # the counters before the sample: it must see the fill level the store left, as the eager
         # frame's does
-        L = _lib.load()
-        with torch.cuda.device(env.device):
-            _lib.check(L.pbn_replay_advance(env.n_alloc, rp.capacity, self._pos_t.data_ptr(), self._size_t.data_ptr(),
-                                            self._step_t.data_ptr(), self._eps64.data_ptr(), self._eps32.data_ptr(),
-                                            float(self.min_epsilon), float(self.epsilon_decrement), 0, 0, None, None,
-                                            env._stream()), "pbn_replay_advance")
+        self._advance_counters()
         self._g_idx, self._g_w = rp.sample(self.batch_size, size_t=self._size_t)
         fu.update(rp, self._g_idx, weights=self._g_w, priorities_out=self._prio,
                   replay_constant=self.replay_constant)
         rp.update_priorities(self._g_idx, self._prio, self._size_t)
         with torch.cuda.device(env.device):
-            _lib.check(L.pbn_ddqn_schedule(rp.beta_t.data_ptr(), float(self.beta_increment), self._step_t.data_ptr(),
-                                           self._step_base, self.target_update, fu.t_flat.data_ptr(),
-                                           fu.q_flat.data_ptr(), fu.q_flat.numel(), fu.t_image.data_ptr(),
-                                           fu.q_image.data_ptr(), fu.q_image.numel(), env._stream()),
-                       "pbn_ddqn_schedule")
+            _lib.check(_lib.load().pbn_ddqn_schedule(
+                rp.beta_t.data_ptr(), float(self.beta_increment), self._step_t.data_ptr(), self._step_base,
+                self.target_update, fu.t_flat.data_ptr(), fu.q_flat.data_ptr(), fu.q_flat.numel(),
+                fu.t_image.data_ptr(), fu.q_image.data_ptr(), fu.q_image.numel(), env._stream()), "pbn_ddqn_schedule")
 
     def _mirror(self, k: int) -> None:
         """The host's copies after ``k`` replays: the eager frame's own arithmetic, ``k`` times."""
-        env, rp, fu = self.env, self.replay, self.fused
+        rp, fu = self.replay, self.fused
         synced = False
         for _ in range(k):
             f = self.frames
-            env.step_index += 1
-            rp.pos = (rp.pos + env.n_alloc) % rp.capacity
-            rp.size = min(rp.size + env.n_alloc, rp.capacity)
+            self._mirror_frame()
             rp.beta = self.last_beta = self.beta     # the beta this frame's sample read
             rp.mirror_beta()
             self.updates += 1
-            self.epsilon = max(self.min_epsilon, self.epsilon - self.epsilon_decrement)
             if (f + 1) % self.target_update == 0:
                 self.syncs.append(f)
                 synced = True
@@ -719,8 +630,7 @@ class DDQNLearner:
         # version counters are what sync(), BatchedDDQN and PyTorch read)
         fu.mark_updated()
         if synced:
-            fu._bump(fu._tp)
-            fu._tv = fu._versions(fu._tp)
+            fu.mark_target_updated()
         self.last_loss = fu.loss[0]
 
     def run(self, k: int):

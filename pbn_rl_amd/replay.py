@@ -26,6 +26,9 @@ MSE loss, gradients clamped to [-1, 1] (:129-130), one Adam step, and every
 ``PrioritisedDeviceReplay`` adds the other half of the reference's replay module,
 ``PrioritisedER`` (bdq_model/memory.py:73-186): proportional prioritised replay over a sum and a
 min segment tree, held on the device (csrc/pbn_per.hip; DESIGN.md "Prioritised replay").
+
+``FusedBDQUpdate`` is the update as HIP launches (its buffers and their bookkeeping: fused.py), and
+``BDQLearner`` the training loop (the plumbing of its graph-captured frame: learner.py).
 """
 from __future__ import annotations
 
@@ -37,6 +40,8 @@ import torch.nn.functional as F
 
 from . import _lib
 from .agent import BatchedBDQ, BranchingQNetwork
+from .fused import FusedUpdate, bump
+from .learner import FrameLearner
 from .vector_env import VectorPBNEnv
 
 __all__ = ["DeviceReplay", "PrioritisedDeviceReplay", "bdq_update", "soft_update", "BDQLearner", "FusedBDQUpdate",
@@ -148,12 +153,21 @@ class DeviceReplay:
         """Fill ``idx_out`` (int64) with rows uniform over [0, size) with replacement, from the
         Philox REPLAY stream of (seed, row, *counter_t) (pbn_replay_advance; counter_t advances):
         one launch, graph-capturable, and the same rows eager or captured."""
-        L = _lib.load()
-        with torch.cuda.device(self.device):
-            _lib.check(L.pbn_replay_advance(0, self.capacity, None, size_t.data_ptr(), None, None, None, 0.0, 0.0,
-                                            idx_out.numel(), seed, counter_t.data_ptr(), idx_out.data_ptr(),
-                                            torch.cuda.current_stream(self.device).cuda_stream), "pbn_replay_advance")
+        self.advance(0, None, size_t, None, None, None, 0.0, 0.0, seed, counter_t, idx_out)
         return idx_out
+
+    def advance(self, n_store: int, pos_t, size_t, step_t, eps64, eps32, eps_floor: float, eps_step: float, seed: int,
+                counter_t=None, idx_out=None) -> None:
+        """pbn_replay_advance, one launch on one-element device tensors (None: left alone): the ring
+        position and fill level move on by ``n_store`` rows, ``*step_t`` by one, epsilon (a double
+        and its float copy) down by ``eps_step`` to ``eps_floor``; then ``idx_out``, if given, is
+        filled as ``sample_rows`` describes, over the new fill level."""
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().pbn_replay_advance(
+                n_store, self.capacity, ptr(pos_t), ptr(size_t), ptr(step_t), ptr(eps64), ptr(eps32), eps_floor,
+                eps_step, 0 if idx_out is None else idx_out.numel(), seed, ptr(counter_t), ptr(idx_out),
+                torch.cuda.current_stream(self.device).cuda_stream), "pbn_replay_advance")
 
     def gather(self, idx: torch.Tensor, net_handle, stream=None) -> Dict[str, torch.Tensor]:
         """Rows ``idx`` (B a multiple of 32) as network inputs, in one launch (``pbn_replay_batch``):
@@ -452,63 +466,39 @@ def _bdq_segments(q: BranchingQNetwork):
     return out
 
 
-class FusedBDQUpdate:
+class FusedBDQUpdate(FusedUpdate):
     """update_policy (bdq_model/__init__.py:100-139) as three HIP launches (``pbn_bdq_learn``,
     csrc/pbn_learn.hip) instead of ~100 PyTorch kernels: the online and target networks' forwards,
     the double-DQN TD loss, the backward, the gradient clamp and the Adam step.
 
-    The networks' parameters move into one flat fp32 buffer each (``pbn_bdq_layout``); their
-    nn.Parameters become views of it, so ``state_dict``, the PyTorch forward and the acting kernel
-    see the same weights.  Each network also has an image (``q_image`` / ``t_image``, pbn_bdq_pack):
-    its bilinear target table (``q_table``, the acting kernel's operand), then its dense weights
-    as 16 x 16 tiles in the update kernels' MFMA-fragment orders.  The online image is rewritten by
-    every update; ``pack()`` recomputes the images after weights change any other way (a loaded
-    checkpoint), ``soft_update()`` moves the target network halfway (bdq_model/__init__.py:137-139)
-    and repacks its image.  Adam (torch.optim.Adam's arithmetic,
-    betas (0.9, 0.999), eps 1e-8) keeps its moments in buffers of the same layout and its step
-    count on the device (graph-capturable)."""
+    The buffers and their bookkeeping are FusedUpdate's (fused.py); the flat layout is
+    ``pbn_bdq_layout``.  A network's image (pbn_bdq_pack) is its bilinear target table (``q_table``,
+    the acting kernel's operand), then its dense weights as 16 x 16 tiles in the update kernels'
+    MFMA-fragment orders.  The online image is rewritten by every update; ``pack()`` recomputes the
+    images after weights change any other way (a loaded checkpoint), ``soft_update()`` moves the
+    target network halfway (bdq_model/__init__.py:137-139) and repacks its image.  Adam is
+    torch.optim.Adam's arithmetic, betas (0.9, 0.999), eps 1e-8."""
 
     def __init__(self, q: BranchingQNetwork, target: BranchingQNetwork, net, branches: int, *, batch_size: int,
                  learning_rate: float = 1e-4, gamma: float = 0.999, grad_clamp: float = 1.0,
                  betas=(0.9, 0.999), eps: float = 1e-8, keep_grad: bool = False):
         spec = net.spec
         N = spec.n
-        dev = next(q.parameters()).device
-        if dev.type != "cuda":
-            raise ValueError("FusedBDQUpdate runs on the GPU")
+        self._require_gpu(q)
         for m in (q, target):
             if (not isinstance(m, BranchingQNetwork) or m.n != branches or m.ac_dim != N + 1
                     or m.model[0].input1_dim != N or m.model[0].input2_dim != N):
                 raise ValueError("FusedBDQUpdate needs BranchingQNetwork((N, N), N + 1, branches) for both networks")
-        self.net, self.N, self.K, self.B = net, N, int(branches), int(batch_size)
-        self.lr, self.gamma, self.grad_clamp = float(learning_rate), float(gamma), float(grad_clamp)
-        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        self.K, self.grad_clamp = int(branches), float(grad_clamp)
         self.slope = float(q.model[1].negative_slope)
         self.off = bdq_layout(N, self.K)
-        self.q_flat = self._flatten(q, dev)
-        self.t_flat = self._flatten(target, dev)
-        self.q, self.target = q, target
-        self._qp, self._tp = list(q.parameters()), list(target.parameters())
-        self._qv = self._tv = None
-        self.m = torch.zeros_like(self.q_flat)
-        self.v = torch.zeros_like(self.q_flat)
-        self.step = torch.zeros(1, dtype=torch.float32, device=dev)
+        super().__init__(q, target, net, batch_size=batch_size, learning_rate=learning_rate, gamma=gamma, betas=betas,
+                         eps=eps, keep_grad=keep_grad)
+        # each image begins with the bilinear target table, which the acting kernel reads (a view)
         n_attr = len(spec.attractors)
-        L = _lib.load()
-        # each network's image (pbn_bdq_pack): the bilinear target table, which the acting kernel
-        # reads (q_table, a view), then the dense weights in the update kernels' fragment orders
-        nimg = ctypes.c_int64()
-        _lib.check(L.pbn_bdq_image_floats(net.handle, self.K, ctypes.byref(nimg)), "pbn_bdq_image_floats")
-        self.q_image = torch.zeros(nimg.value, dtype=torch.float32, device=dev)
-        self.t_image = torch.zeros_like(self.q_image)
         nt = n_attr * N * 256
         self.q_table = self.q_image[:nt].view(n_attr, N, 16, 16)
         self.t_table = self.t_image[:nt].view(n_attr, N, 16, 16)
-        nbytes = ctypes.c_int64()
-        _lib.check(L.pbn_bdq_learn_workspace(N, self.K, self.B, ctypes.byref(nbytes)), "pbn_bdq_learn_workspace")
-        self.work = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=dev)
-        self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.grad = torch.zeros_like(self.q_flat) if keep_grad else None
         H, A = self.K + 1, N + 1
         o = self.off
         self._acting = (None, self.q_flat[o[1]:o[1] + 256],
@@ -516,85 +506,31 @@ class FusedBDQUpdate:
                          self.q_flat[o[10]:o[10] + H * A * 64].view(H, A, 64),
                          self.q_flat[o[11]:o[11] + H * A].view(H, 1, A)),
                         self.q_table)
-        self.pack()
 
-    def _flatten(self, q: BranchingQNetwork, dev) -> torch.Tensor:
-        flat = torch.zeros(self.off[12], dtype=torch.float32, device=dev)
-        with torch.no_grad():
-            for p, seg, extra in _bdq_segments(q):
-                at = self.off[seg] + extra
-                view = flat[at:at + p.numel()].view(p.shape)
-                view.copy_(p.detach())
-                p.data = view
-        return flat
-
-    def _stream(self):
-        return torch.cuda.current_stream(self.q_flat.device).cuda_stream
-
-    @staticmethod
-    def _versions(params) -> tuple:
-        return tuple(p._version for p in params)
-
-    @staticmethod
-    def _bump(params) -> None:
-        """Mark parameters the HIP kernels rewrote in place (their version counters are how
-        PyTorch, and BatchedBDQ's eval-mode pack cache, see an in-place change)."""
-        for p in params:
-            torch.autograd.graph.increment_version(p)
-
-    def pack(self, which: str = "both") -> None:
-        """Recompute the images (pbn_bdq_pack: the bilinear target table and the fragment-ordered
-        dense weights) of the online and/or target network."""
+    def _sizes(self):
         L = _lib.load()
-        with torch.cuda.device(self.q_flat.device):
-            for name, flat, image in (("online", self.q_flat, self.q_image), ("target", self.t_flat, self.t_image)):
-                if which in ("both", name):
-                    _lib.check(L.pbn_bdq_pack(self.net.handle, self.K, flat.data_ptr(), image.data_ptr(),
-                                              self._stream()), "pbn_bdq_pack")
-        if which in ("both", "online"):
-            self._qv = self._versions(self._qp)
-        if which in ("both", "target"):
-            self._tv = self._versions(self._tp)
+        nimg, nbytes = ctypes.c_int64(), ctypes.c_int64()
+        _lib.check(L.pbn_bdq_image_floats(self.net.handle, self.K, ctypes.byref(nimg)), "pbn_bdq_image_floats")
+        _lib.check(L.pbn_bdq_learn_workspace(self.N, self.K, self.B, ctypes.byref(nbytes)), "pbn_bdq_learn_workspace")
+        return self.off[12], nimg.value, nbytes.value
 
-    def sync(self) -> None:
-        """Repack the table of a network whose parameters changed since its last pack (e.g. a
-        load_state_dict: the copy bumps the parameters' versions); a no-op otherwise."""
-        if self._versions(self._qp) != self._qv:
-            self.pack("online")
-        if self._versions(self._tp) != self._tv:
-            self.pack("target")
+    def _params(self, q: BranchingQNetwork):
+        return [(p, self.off[seg] + extra) for p, seg, extra in _bdq_segments(q)]
 
-    def mark_updated(self) -> None:
-        """After a pbn_bdq_learn launch (eager, or a replayed graph holding one): the online
-        parameters changed in place."""
-        self._bump(self._qp)
-        self._qv = self._versions(self._qp)
+    def _pack(self, flat: torch.Tensor, image: torch.Tensor) -> None:
+        _lib.check(_lib.load().pbn_bdq_pack(self.net.handle, self.K, flat.data_ptr(), image.data_ptr(), self._stream()),
+                   "pbn_bdq_pack")
 
     def soft_update(self) -> None:
         """target <- target / 2 + online / 2 (soft_update's arithmetic, one pass over the buffer)."""
         with torch.no_grad():
             self.t_flat.div_(2).add_(self.q_flat / 2)
-        self._bump(self._tp)
+        self.mark_target_updated()
         self.pack("target")
 
     def acting_pack(self):
         """BatchedBDQ's weight-derived operands as views of the flat buffer (no assembly kernels)."""
         return self._acting
-
-    @staticmethod
-    def check_per_args(B: int, device, weights, priorities_out) -> None:
-        """update()'s importance-weight arguments: both or neither, contiguous float32 [B] tensors
-        on ``device``.  Raises ValueError naming the offending argument."""
-        if weights is None:
-            if priorities_out is not None:
-                raise ValueError("priorities_out needs weights")
-            return
-        if priorities_out is None:
-            raise ValueError("priorities_out is required with weights")
-        for name, t in (("weights", weights), ("priorities_out", priorities_out)):
-            if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.shape != (B,)
-                    or not t.is_contiguous() or t.device != torch.device(device)):
-                raise ValueError(f"{name} must be a contiguous float32 [{B}] tensor on {device}")
 
     def update(self, replay: "DeviceReplay", idx: torch.Tensor, advance=None, weights: Optional[torch.Tensor] = None,
                priorities_out: Optional[torch.Tensor] = None, replay_constant: float = 1e-5) -> torch.Tensor:
@@ -607,8 +543,7 @@ class FusedBDQUpdate:
         position): the weighted update of bdq_update, loss = mean_b w_b l_b, as the same three
         launches (``pbn_bdq_learn_per``); ``priorities_out`` (float32 [B], required with weights)
         receives |w_b l_b| + ``replay_constant`` from the backward's TD pass."""
-        if idx.shape != (self.B,) or idx.dtype != torch.int64:
-            raise ValueError(f"idx must be {self.B} int64 ring indices")
+        self._check_idx(idx)
         self.check_per_args(self.B, self.q_flat.device, weights, priorities_out)
         self.sync()
         L = _lib.load()
@@ -632,16 +567,8 @@ class FusedBDQUpdate:
             self.mark_updated()   # (a captured update is marked by each replay: BDQLearner._replay_frame)
         return self.loss[0]
 
-    def grads(self) -> List[torch.Tensor]:
-        """The last update's clamped gradient (keep_grad=True) as views shaped like q.parameters()."""
-        if self.grad is None:
-            raise ValueError("construct with keep_grad=True")
-        g = {id(p): self.grad[self.off[seg] + extra:self.off[seg] + extra + p.numel()].view(p.shape)
-             for p, seg, extra in _bdq_segments(self.q)}
-        return [g[id(p)] for p in self.q.parameters()]
 
-
-class BDQLearner:
+class BDQLearner(FrameLearner):
     """BranchingDQN.learn (bdq_model/__init__.py:150-238) over a VectorPBNEnv: every frame acts
     for all envs (BatchedBDQ), appends their transitions to the device replay, and, once
     ``learning_starts`` transitions are stored, takes ``updates_per_frame`` update_policy steps.
@@ -782,8 +709,6 @@ class BDQLearner:
                     self.last_loss = self._update_prioritised()
                 elif self.fused is not None:
                     self.last_loss = self.fused.update(self.replay, self._idx[u * self.batch_size:(u + 1) * self.batch_size])
-                elif self.prioritised:
-                    self.last_loss = self._update_prioritised()
                 else:
                     self.last_loss = self._update(self.replay.sample_indices(self.batch_size, self.gen))
                 self.updates += 1
@@ -802,8 +727,6 @@ class BDQLearner:
             self._refresh_target_weights()
 
     def _update(self, idx: torch.Tensor) -> torch.Tensor:
-        if self.fused is not None:
-            return self.fused.update(self.replay, idx)
         batch = self.replay.gather(idx, self.env.net)
         return bdq_update(self.q, self.target, self.opt, batch, self.gamma, target_weights=self._target_weights())
 
@@ -814,11 +737,10 @@ class BDQLearner:
         if self.fused is not None:   # the weights into, and the priorities out of, the fused update's TD pass
             loss = self.fused.update(rp, idx, weights=w, priorities_out=self._prio,
                                      replay_constant=self.replay_constant)
-            rp.update_priorities(idx, self._prio, size_t)
-            return loss
-        batch = rp.gather(idx, self.env.net)
-        loss = bdq_update(self.q, self.target, self.opt, batch, self.gamma, target_weights=self._target_weights(),
-                          weights=w, priorities_out=self._prio, replay_constant=self.replay_constant)
+        else:
+            loss = bdq_update(self.q, self.target, self.opt, rp.gather(idx, self.env.net), self.gamma,
+                              target_weights=self._target_weights(), weights=w, priorities_out=self._prio,
+                              replay_constant=self.replay_constant)
         rp.update_priorities(idx, self._prio, size_t)
         return loss
 
@@ -847,27 +769,10 @@ class BDQLearner:
             raise ValueError("target_update must be a multiple of updates_per_frame")
         env = self.env
         dev = env.device
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            while self.replay.size < self.learning_starts or self.updates < min_updates:
-                self.frame()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        self._step_t = torch.full((1,), env.step_index, dtype=torch.int64, device=dev)
-        self._eps64 = torch.full((1,), self.epsilon, dtype=torch.float64, device=dev)
-        self._eps32 = self._eps64.float()
-        self._pos_t = torch.full((1,), self.replay.pos, dtype=torch.int64, device=dev)
-        self._size_t = torch.full((1,), self.replay.size, dtype=torch.int64, device=dev)
+        self._warm_up(lambda: self.replay.size >= self.learning_starts and self.updates >= min_updates)
+        self._capture_counters(self.epsilon_final, self.epsilon_step, self.seed)
         self._done_buf = torch.zeros(env.n_alloc, dtype=torch.uint8, device=dev)
-        self._tgt_prev = env.target.clone()   # the pre-step targets, carried by the ring store
-        # under the one-update law the step kernel writes the ring rows itself (pbn_step_dev_store)
-        self._ring = None
-        if env.spec.settle < 2:
-            rp = self.replay
-            self._ring = _lib.RingStore(
-                rp.capacity, self._pos_t.data_ptr(), rp.state.data_ptr(), rp.next_state.data_ptr(), rp.target.data_ptr(),
-                rp.action.data_ptr(), rp.reward.data_ptr(), rp.done.data_ptr(), self.agent.actions.data_ptr(),
-                rp.action.shape[1], _lib.FLAG_TERMINATED | _lib.FLAG_TRUNCATED, self._done_buf.data_ptr())
+        self._capture_ring(_lib.FLAG_TERMINATED | _lib.FLAG_TRUNCATED, self._done_buf, self.agent.actions)
         self._adv = None
         if self.fused is not None and not self.prioritised:
             # the fused update's last launch advances the frame's counters and draws the next
@@ -893,35 +798,14 @@ class BDQLearner:
     def _graph_body(self):
         env = self.env
         self.agent.act_q(step_t=self._step_t, epsilon_t=self._eps32)
-        if self._ring is not None:
-            # one launch: the step, in place, writing its transitions into the ring
-            env.step_flipmask_dev_store(self._step_t, self._ring)
-            if self.prioritised:   # (the new rows' priorities; the position advances below)
-                self.replay.store_priorities(env.n_alloc, self._pos_t)
-        else:
-            env.step_flipmask_dev(self._step_t, copy_back=False)
-            # the ring store reads the pre-step state (still in env.state) and target (carried in
-            # _tgt_prev), derives done from the flags, and in the same pass moves the stepped state
-            # into env.state and the new targets into _tgt_prev
-            self.replay.store_at(self._pos_t, self._size_t, env.state, self._tgt_prev, self.agent.actions,
-                                 env.reward, env.final_state, env.flags,
-                                 done_mask=_lib.FLAG_TERMINATED | _lib.FLAG_TRUNCATED, done_out=self._done_buf,
-                                 advance=False, state_copy=(env.state, env._state_next),
-                                 target_copy=(self._tgt_prev, env.target))
+        self._step_and_store()
         # then the counters: the step index, the ring position and fill level, epsilon (and, fused,
         # the next frame's rows) advance in the update's last launch or in pbn_replay_advance.  A
         # prioritised frame, fused or not, advances them before its updates: its sample must see the
         # fill level after the frame's store, as the eager path does
         fused = self.fused is not None and not self.prioritised
-        L = _lib.load()
         if not fused:   # (fused: the update's last launch advances them, pbn_frame_advance)
-            with torch.cuda.device(env.device):
-                _lib.check(L.pbn_replay_advance(env.n_alloc, self.replay.capacity, self._pos_t.data_ptr(),
-                                                self._size_t.data_ptr(), self._step_t.data_ptr(),
-                                                self._eps64.data_ptr(), self._eps32.data_ptr(),
-                                                float(self.epsilon_final), float(self.epsilon_step), 0, self.seed,
-                                                None, None, torch.cuda.current_stream(env.device).cuda_stream),
-                           "pbn_replay_advance")
+            self._advance_counters()
         loss = None
         B = self.batch_size
         U = self.updates_per_frame
@@ -936,7 +820,7 @@ class BDQLearner:
         return env.reward[: env.num_envs], self._done_buf[: env.num_envs].view(torch.bool), loss
 
     def _replay_frame(self):
-        env, rp = self.env, self.replay
+        rp = self.replay
         if self.fused is not None:
             self.fused.sync()            # weights loaded between replays: repack the tables
         else:
@@ -947,11 +831,8 @@ class BDQLearner:
         if self.fused is not None:
             self.fused.mark_updated()
         else:
-            FusedBDQUpdate._bump(self.q.parameters())
-        env.step_index += 1
-        rp.pos = (rp.pos + env.n_alloc) % rp.capacity
-        rp.size = min(rp.size + env.n_alloc, rp.capacity)
-        self.epsilon = max(self.epsilon_final, self.epsilon - self.epsilon_step)
+            bump(self.q.parameters())
+        self._mirror_frame()
         if self.prioritised:
             for _ in range(self.updates_per_frame):
                 rp.mirror_beta()

@@ -249,6 +249,36 @@ def test_fused_learner_loads_a_checkpoint():
     assert torch.isfinite(lr.last_loss)
 
 
+def test_captured_fused_learner_uses_weights_loaded_between_replays():
+    """A captured learner picks up weights loaded with load_state_dict between replays through
+    sync() alone (no refresh_weights()): it stays bit-equal to an eager learner given the same
+    weights at the same frame, and the target image the replays read is a repacked one."""
+    env_e, eager = _learner(256, 3, True)
+    env_g, graph = _learner(256, 3, True)
+    graph.capture()
+    for _ in range(graph.frames):
+        eager.frame()
+    torch.manual_seed(9)
+    src = BranchingQNetwork((28, 28), 29, 3).cuda()
+    with torch.no_grad():
+        for p in src.parameters():
+            p.mul_(-1.5)
+    torch.cuda.synchronize()
+    t_image_before = graph.fused.t_image.clone()
+    for lr in (eager, graph):
+        lr.q.load_state_dict(src.state_dict())
+        lr.target.load_state_dict(src.state_dict())
+    for k in range(3):
+        eager.frame()
+        graph.frame()
+        torch.cuda.synchronize()
+        assert torch.equal(eager.last_loss, graph.last_loss), k
+    assert eager.updates == graph.updates
+    for name in ("q_flat", "t_flat", "q_image", "t_image", "m", "v"):
+        assert torch.equal(getattr(eager.fused, name), getattr(graph.fused, name)), name
+    assert not torch.equal(graph.fused.t_image, t_image_before)
+
+
 def test_fused_update_matches_reference_update_policy():
     """pbn_bdq_learn held to the reference's own update_policy (bdq_model/__init__.py:100-139):
     tests/golden/bdq_update.npz, two calls of that method's source on the reference network
