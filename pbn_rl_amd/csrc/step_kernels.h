@@ -247,6 +247,83 @@ __device__ __forceinline__ T& lane_at(T* base, size_t uniform_elems, uint32_t la
 #else
 #define LANE_ST(base, ubase, le_, len, site, v) (LANE_AT(base, ubase, le_, len, site) = (v))
 #endif
+// One per-step output of pbn_rollout_pipe ([n_steps][W][n] elements of T), stored through a
+// buffer descriptor that covers ONE row of n elements: the row of step t, word 0.  The
+// descriptor lives in four SGPRs, is built once before the step loop and moves on by one step
+// with a 64-bit add to its base (so n_steps * W * n * sizeof(T) may pass 4 GB), where
+// global_store's saddr form took a 64-bit multiply, shift and add per store and step.  The
+// hardware's range check (raw buffer, stride 0: the lane's byte offset + sizeof(T) must not pass
+// num_records; soffset stays 0) replaces the guards:
+//   - a null output has num_records = 0, so every store to it is dropped;
+//   - a lane of an invalid group (env le >= n) has offset le * sizeof(T) >= n * sizeof(T) =
+//     num_records, so its store is dropped: no EXEC mask, and no lane can reach the next word's
+//     row, the next step's row or another array.
+// Word w > 0 of a multi-word state is a copy of the descriptor moved on by w rows.  Non-temporal
+// as LANE_ST.  The stores are inline assembly because the compiler rebuilds a
+// __builtin_amdgcn_make_buffer_rsrc descriptor from its pointer on every step (four SALU
+// instructions each); the kernel never reads these arrays back, so the statements need no
+// memory clobber and LDS traffic may move across them.  Checked builds (PBN_CHECKS) keep the
+// guarded, bounds-checked index.
+typedef uint32_t pbn_u32x4 __attribute__((ext_vector_type(4)));
+template <typename T>
+struct StepRows {
+#ifndef PBN_CHECKS
+  pbn_u32x4 d;      // base[31:0] | base[47:32], stride 0 | num_records (bytes) | format word
+#else
+  T* base;
+  size_t at, len;   // first element of the current step's row; elements in all
+#endif
+};
+template <typename T>
+__device__ __forceinline__ StepRows<T> rows_open(T* base, int64_t n, size_t len) {
+  static_assert(sizeof(T) == 4 || sizeof(T) == 1, "dword and byte stores only");
+  StepRows<T> r;
+#ifndef PBN_CHECKS
+  const uint64_t p = (uint64_t)reinterpret_cast<uintptr_t>(base);
+  r.d.x = (uint32_t)p;
+  r.d.y = (uint32_t)(p >> 32) & 0xFFFFu;
+  r.d.z = base ? (uint32_t)n * (uint32_t)sizeof(T) : 0u;   // n < 2^30 (the host checks it)
+  r.d.w = 0x00020000u;                                       // untyped 32-bit data, no swizzle
+#else
+  r.base = base;
+  r.at = 0;
+  r.len = len;
+#endif
+  return r;
+}
+// moves the descriptor on by `elems` elements (one step: W * n)
+template <typename T>
+__device__ __forceinline__ void rows_advance(StepRows<T>& r, size_t elems) {
+#ifndef PBN_CHECKS
+  const uint64_t b = (((uint64_t)r.d.y << 32) | r.d.x) + (uint64_t)elems * sizeof(T);
+  r.d.x = (uint32_t)b;
+  r.d.y = (uint32_t)(b >> 32);   // (a 48-bit address: no carry into the stride field)
+#else
+  r.at += elems;
+#endif
+}
+// element le of the current step's row of word w (word_elems = w * n)
+// (bits: the element's bit pattern; a byte store writes the low byte)
+template <typename T>
+__device__ __forceinline__ void rows_store(const StepRows<T>& r, int w, size_t word_elems, int64_t le, bool valid,
+                                           int site, uint32_t bits) {
+#ifndef PBN_CHECKS
+  StepRows<T> q = r;
+  if (w > 0) rows_advance(q, word_elems);
+  const uint32_t off = (uint32_t)le * (uint32_t)sizeof(T);
+  if constexpr (sizeof(T) == 4)
+    asm volatile("buffer_store_dword %0, %1, %2, 0 offen nt" ::"v"(bits), "v"(off), "s"(q.d));
+  else
+    asm volatile("buffer_store_byte %0, %1, %2, 0 offen nt" ::"v"(bits), "v"(off), "s"(q.d));
+#else
+  if (valid && r.base) {
+    T v;
+    __builtin_memcpy(&v, &bits, sizeof(T));   // (little-endian: the low byte)
+    r.base[CK(r.at + word_elems + (size_t)le, r.len, site)] = v;
+  }
+#endif
+}
+
 // LANE_ST with a per-lane element index (pbn_rollout_settle: every env is at its own step, so
 // the step's base is not wave-uniform).  Write-back stores, not streaming ones: the few lanes
 // that end a step in an iteration each write one element of a different output row, and a
@@ -1521,7 +1598,7 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
   if (role == 1 && (u_fl & 4u) && u_gx == 2 && u_na >= 2 && (u_fl & 16u) && (W > 1 || N <= 31)) {
     // env draws, common configuration (random actions, gap bucket table, two or more
     // single-state attractors): the same draws as the general loop below, branch-free apart from
-    // the rare fourth-flip tail and the guarded flip-mask store, so that the next step's ENV call
+    // the rare fourth-flip tail, so that the next step's ENV call
     // (computed here, one step ahead) interleaves with this step's dependent draws and LDS reads
     // instead of following them
     const uint32_t A = (uint32_t)u_na;
@@ -1533,14 +1610,16 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
       const uint32_t ge_hi = (uint32_t)((ge >> 32) & 0xFFFFu) | ((uint32_t)((step >> 32) & 0xFFFFu) << 16);
       return pbn::philox((uint32_t)ge, (uint32_t)step, pbn::kStreamEnv << 28, ge_hi, u_k0, u_k1);
     };
-    // one step: this step's draws from E, the next step's ENV call into E_next
-    auto env_step = [&](int k, const Word4& E, Word4& E_next) {
+    StepRows<uint32_t> fm_rows = rows_open(a.flipmask, n, (size_t)n_steps * plane);
+    // one step (k < n_steps; `odd` = k & 1, known at compile time: the slot costs no select):
+    // this step's draws from E, the next step's ENV call into E_next
+    auto env_step = [&](int k, auto odd, const Word4& E, Word4& E_next) {
       asm volatile("" : "+s"(u_k0), "+s"(u_k1), "+s"(u_gx), "+s"(u_na), "+s"(u_mnf));
       asm volatile("" : "+s"(u_hb), "+s"(u_hp), "+s"(u_hz), "+s"(u_fl));
       PBN_ISA_LOOP("env_fast", W);
       PBN_PSTAMP(k, 0);
-      if (k < n_steps) {
-        uint32_t* slot = slots + (size_t)(k & 1) * a.slot_words;
+      {
+        uint32_t* slot = slots + (decltype(odd)::value ? (size_t)a.slot_words : (size_t)0);
         // part 1: the draws that feed LDS reads, and the reads themselves
         uint32_t xhi = E.w, xlo = E.z;
         const uint32_t c_act = ext64(xhi, xlo, n1 * n1 * n1);
@@ -1596,10 +1675,9 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
           slot[(2 * W + w) * 64 + lane] = rs[w];
         }
         slot[3 * W * 64 + lane] = rt | (pc << 8) | ((uint32_t)pert << 16);
-        if (valid) {
 #pragma unroll
-          for (int w = 0; w < W; ++w) LANE_ST(a.flipmask, k * plane + (size_t)w * n, le, (size_t)n_steps * plane, 8, m[w]);
-        }
+        for (int w = 0; w < W; ++w) rows_store(fm_rows, w, (size_t)w * n, le, valid, 8, m[w]);
+        rows_advance(fm_rows, plane);
         if (p2 < N - 1) {   // rare: a fourth flip is possible (gap k >= 3: PERT call (k-3)>>2, word (k-3)&3)
           const uint64_t step = a.step + (uint64_t)k;
           const uint32_t ge_hi = (uint32_t)((ge >> 32) & 0xFFFFu) | ((uint32_t)((step >> 32) & 0xFFFFu) << 16);
@@ -1626,13 +1704,19 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
       lds_barrier();
       PBN_PSTAMP(k, 2);
     };
-    // two steps per trip with the ENV words alternating between EA and EB: no copies between steps
+    // two steps per trip with the ENV words alternating between EA and EB: no copies between
+    // steps; the block's last barrier (the state wave's step n_steps - 1) follows the loop
     Word4 EA = env_call(0), EB = EA;
-    for (int k = 0; k <= n_steps; k += 2) {
-      env_step(k, EA, EB);
-      if (k + 1 <= n_steps) env_step(k + 1, EB, EA);
+    for (int k = 0; k < n_steps; k += 2) {
+      env_step(k, std::false_type{}, EA, EB);
+      if (k + 1 < n_steps) env_step(k + 1, std::true_type{}, EB, EA);
     }
+    PBN_PSTAMP(n_steps, 0);
+    PBN_PSTAMP(n_steps, 1);
+    lds_barrier();
+    PBN_PSTAMP(n_steps, 2);
   } else if (role == 1) {
+    StepRows<uint32_t> fm_rows = rows_open(a.flipmask, n, (size_t)n_steps * plane);
     for (int k = 0; k <= n_steps; ++k) {
       asm volatile("" : "+s"(u_k0), "+s"(u_k1), "+s"(u_gx), "+s"(u_na), "+s"(u_mnf));
       asm volatile("" : "+s"(u_hb), "+s"(u_hp), "+s"(u_hz), "+s"(u_fl));
@@ -1647,6 +1731,8 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
         // one ENV call: words 0, 1 = gaps 0, 1; X = words 3:2 gives, in order, the action draw
         // (every mode), the autoreset draws and gap 2's uniform u2 (DESIGN.md "Step semantics")
         const Word4 E = pbn::philox(ge_lo, st_lo, pbn::kStreamEnv << 28, ge_hi, u_k0, u_k1);
+        StepRows<uint32_t> fm_k = fm_rows;   // (the store sits in a divergent arm: the step's advance here)
+        rows_advance(fm_rows, plane);
         if (valid) {
           uint32_t m[W], gam[W], rs[W];
 #pragma unroll
@@ -1693,7 +1779,7 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
           if (u_fl & 4u) {
             actions_from_draw<W>(c_act, N, a.n1_magic, m);
 #pragma unroll
-            for (int w = 0; w < W; ++w) LANE_ST(a.flipmask, k * plane + (size_t)w * n, le, (size_t)n_steps * plane, 8, m[w]);
+            for (int w = 0; w < W; ++w) rows_store(fm_k, w, (size_t)w * n, le, valid, 8, m[w]);
           } else {
 #pragma unroll
             for (int w = 0; w < W; ++w)
@@ -1763,18 +1849,18 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
         }
       };
       // one step: this step's compares from `cur`, the next step's calls into `nxt`
-      auto sel_step = [&](int k, const uint32_t (&cur)[16], uint32_t (&nxt)[16]) {
+      auto sel_step = [&](int k, auto odd, const uint32_t (&cur)[16], uint32_t (&nxt)[16]) {
         asm volatile("" : "+s"(u_k0), "+s"(u_k1));
         PBN_ISA_LOOP("sel_fast", NQ);
         PBN_PSTAMP(k, 0);
-        if (k < n_steps) {
+        {
           sel_calls(k + 1, nxt);   // (one unused set per launch)
 #ifdef PBN_STAMPS
 #pragma unroll
           for (int d = 0; d < 16; ++d) asm volatile("" : "+v"(nxt[d]));
 #endif
           PBN_PSTAMP_AT(k, 18);
-          uint32_t* lt_out = lt_base + (size_t)(k & 1) * a.slot_words;
+          uint32_t* lt_out = lt_base + (decltype(odd)::value ? (size_t)a.slot_words : (size_t)0);
 #pragma unroll
           for (int q = 0; q < NQ; ++q)
             lt_out[q * 64] = less_than_cm4<B>(cur, cmi + q * B);
@@ -1791,10 +1877,14 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
 #pragma unroll
       for (int d = 0; d < 16; ++d) { dA[d] = 0; dB[d] = 0; }
       sel_calls(0, dA);
-      for (int k = 0; k <= n_steps; k += 2) {
-        sel_step(k, dA, dB);
-        if (k + 1 <= n_steps) sel_step(k + 1, dB, dA);
+      for (int k = 0; k < n_steps; k += 2) {
+        sel_step(k, std::false_type{}, dA, dB);
+        if (k + 1 < n_steps) sel_step(k + 1, std::true_type{}, dB, dA);
       }
+      PBN_PSTAMP(n_steps, 0);
+      PBN_PSTAMP(n_steps, 1);
+      lds_barrier();   // the block's last barrier: the state wave's step n_steps - 1
+      PBN_PSTAMP(n_steps, 2);
     };
     switch (u_mnf) {
       case 2: sel_fast(std::integral_constant<int, 1>{}); break;
@@ -1850,35 +1940,55 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
   } else {
     // the epilogue of step t (after the back-transpose): perturbed envs, outputs, attractor
     // hash, reward, flags, autoreset
-    auto finish = [&](int t, uint32_t (&sp)[W], const uint32_t (&s1)[W], const uint32_t (&gam)[W],
+    // the per-step outputs, one descriptor each (a null obs / final_state: stores dropped)
+    StepRows<uint32_t> obs_rows = rows_open(a.obs, n, (size_t)n_steps * plane);
+    StepRows<uint32_t> fin_rows = rows_open(a.final_state, n, (size_t)n_steps * plane);
+    StepRows<float> rwd_rows = rows_open(a.reward, n, (size_t)n_steps * n);
+    StepRows<uint8_t> flg_rows = rows_open(a.flags, n, (size_t)n_steps * n);
+    // launch invariants as values instead of tests in the loop: no truncation is a horizon no
+    // step count reaches (t <= 255)
+    u_hz = u_hz > 0 ? u_hz : 0x7FFFFFFF;
+    // the hash's shift (32 - bits) instead of its bit count: 32 = no attractor table
+    int u_hs = u_hb > 0 ? 32 - u_hb : 32;
+    auto store_obs = [&](const uint32_t (&s)[W]) {
+#pragma unroll
+      for (int w = 0; w < W; ++w) rows_store(obs_rows, w, (size_t)w * n, le, valid, 7, s[w]);
+      rows_advance(obs_rows, plane);
+    };
+    auto finish = [&](bool autoreset, uint32_t (&sp)[W], const uint32_t (&s1)[W], const uint32_t (&gam)[W],
                       const uint32_t (&rs)[W], uint32_t info) {
       {
-        // branch-free epilogue (this wave bounds the iteration): only the stores are guarded
+        // branch-free epilogue (this wave bounds the iteration), unguarded stores (StepRows)
         const bool pert = (info >> 16) & 1u;
         const uint32_t pc = (info >> 8) & 0xFFu;
 #pragma unroll
         for (int w = 0; w < W; ++w) sp[w] = pert ? (s1[w] ^ gam[w]) : sp[w];
-        if (valid && (u_fl & 2u)) {
 #pragma unroll
-          for (int w = 0; w < W; ++w) LANE_ST(a.final_state, t * plane + (size_t)w * n, le, (size_t)n_steps * plane, 10, sp[w]);
-        }
+        for (int w = 0; w < W; ++w) rows_store(fin_rows, w, (size_t)w * n, le, valid, 10, sp[w]);
+        rows_advance(fin_rows, plane);
         // reward candidates depend only on popcount(flipmask): one 16-byte row {none, wrong,
         // term, -} read beside the hash
         const float4 r4 = reinterpret_cast<const float4*>(rtab)[pc];
         const float r_none = r4.x, r_wrong = r4.y, r_term = r4.z;
         int att = -1;
-        if (u_hb > 0) {
-          const uint32_t hmask = (1u << u_hb) - 1u;
+        if (u_hs < 32) {
           uint32_t h = 0;
 #pragma unroll
           for (int w = 0; w < W; ++w) h += sp[w] * a.hash_mult[w];
-          h >>= (32 - u_hb);
+          h >>= u_hs;
           // the table is usually collision-free (one probe, h < 2^bits needs no mask); keys
           // are unique, so probe order does not matter
           att = hash_probe<W>(htab, h, sp);
-          for (int pr = 1; pr < u_hp; ++pr) {
-            const int id = hash_probe<W>(htab, (h + pr) & hmask, sp);
-            if (id >= 0) att = id;
+          // further probes (a table with collisions) are a rolled loop behind an unlikely branch,
+          // out of line: unrolled in line, their ~150 instructions sat in the hot loop behind a
+          // branch taken every step
+          if (__builtin_expect(u_hp > 1, 0)) {
+            const uint32_t hmask = 0xFFFFFFFFu >> u_hs;
+#pragma nounroll
+            for (int pr = 1; pr < u_hp; ++pr) {
+              const int id = hash_probe<W>(htab, (h + pr) & hmask, sp);
+              if (id >= 0) att = id;
+            }
           }
         }
         const bool in_attr = att >= 0;
@@ -1886,14 +1996,14 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
         const bool wrong = in_attr && !term;
         int tt = (int)tt0 + 1;
         tt = tt > 255 ? 255 : tt;
-        const bool trunc = u_hz > 0 && tt >= u_hz;
-        const bool reset = (u_fl & 8u) && (term || trunc);
+        const bool trunc = tt >= u_hz;   // (no horizon: INT_MAX)
+        const bool reset = autoreset && (term || trunc);
         const uint32_t fl = (uint32_t)term | ((uint32_t)trunc << 1) | ((uint32_t)in_attr << 2) |
                             ((uint32_t)pert << 3) | ((uint32_t)reset << 4);
-        if (valid) {
-          LANE_ST(a.reward, (size_t)t * n, le, (size_t)n_steps * n, 11, term ? r_term : (wrong ? r_wrong : r_none));
-          LANE_ST(a.flags, (size_t)t * n, le, (size_t)n_steps * n, 15, (uint8_t)fl);
-        }
+        rows_store(rwd_rows, 0, 0, le, valid, 11, __float_as_uint(term ? r_term : (wrong ? r_wrong : r_none)));
+        rows_store(flg_rows, 0, 0, le, valid, 15, fl);   // (fl < 32: one byte)
+        rows_advance(rwd_rows, (size_t)n);
+        rows_advance(flg_rows, (size_t)n);
         tg0 = reset ? (info & 0xFFu) : tg0;
         tt0 = reset ? 0u : (uint32_t)tt;
 #pragma unroll
@@ -1910,8 +2020,19 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
         uint32_t ins[K];
 #pragma unroll
         for (int q = 0; q < K; ++q) ins[q] = recL[q * 32 + l32].x;
-        for (int k = 0; k <= n_steps; ++k) {
-          asm volatile("" : "+s"(u_hb), "+s"(u_hp), "+s"(u_hz), "+s"(u_fl));
+        // iteration 0 (the other waves produce step 0) is the barrier alone, peeled; iteration
+        // k >= 1 runs step t = k - 1 from slot t & 1, whose byte offset toggles by one s_xor
+        PBN_PSTAMP(0, 0);
+        PBN_PSTAMP(0, 1);
+        lds_barrier();
+        PBN_PSTAMP(0, 2);
+        PBN_RSTAMP(3);
+        uint32_t slot_bytes = 0;
+        const uint32_t slot_toggle = (uint32_t)a.slot_words * 4u;
+        // the one launch-invariant condition left in this loop, held as a lane mask
+        const bool autoreset = (u_fl & 8u) != 0;
+        for (int k = 1; k <= n_steps; ++k) {
+          asm volatile("" : "+s"(u_hs), "+s"(u_hp), "+s"(u_hz));
           // the 4K plane addresses of the gathers are re-derived from ins[] every step: hoisted
           // out of the loop they are 4K more live VGPRs, one was spilled, and its reload's
           // s_waitcnt vmcnt(0) waited on the step's streaming stores in the middle of the chain
@@ -1919,9 +2040,9 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
           for (int q = 0; q < K; ++q) asm volatile("" : "+v"(ins[q]));
           PBN_ISA_LOOP("state_fast", K);
           PBN_PSTAMP(k, 0);
-          if (k >= 1) {
-            const int t = k - 1;
-            const uint32_t* slot = slots + (size_t)(t & 1) * a.slot_words;
+          {
+            const uint32_t* slot = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(slots) + slot_bytes);
+            slot_bytes ^= slot_toggle;
             const uint32_t* lt_in = slot + 4 * 64 + half * 32 + l32;
             uint32_t s1[W], gam[W], rs[W];
             s1[0] = st[0] ^ slot[lane];
@@ -1936,7 +2057,7 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
               sa[q] = selq[(2 * q) * 32 + l32];
               sb[q] = selq[(2 * q + 1) * 32 + l32];
             }
-            if (valid && (u_fl & 1u)) LANE_ST(a.obs, (size_t)t * plane, le, (size_t)n_steps * plane, 7, st[0]);
+            store_obs(st);
             PBN_PSTAMP_AT(k, 15);
             Sg[l32] = lane_transpose32(s1[0], lane);
             __builtin_amdgcn_wave_barrier();
@@ -1954,12 +2075,12 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
             uint32_t sp[W];
             sp[0] = lane_transpose32(x, lane);
             PBN_PSTAMP_AT(k, 13);
-            finish(t, sp, s1, gam, rs, info);
+            finish(autoreset, sp, s1, gam, rs, info);
           }
           PBN_PSTAMP(k, 1);
           lds_barrier();
           PBN_PSTAMP(k, 2);
-          if (k <= 1) PBN_RSTAMP(3 + k);
+          if (k == 1) PBN_RSTAMP(4);
         }
       };
       switch (u_mnf) {
@@ -1971,7 +2092,7 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
     } else
     for (int k = 0; k <= n_steps; ++k) {
       asm volatile("" : "+s"(u_k0), "+s"(u_k1), "+s"(u_gx), "+s"(u_na), "+s"(u_mnf));
-      asm volatile("" : "+s"(u_hb), "+s"(u_hp), "+s"(u_hz), "+s"(u_fl));
+      asm volatile("" : "+s"(u_hs), "+s"(u_hp), "+s"(u_hz), "+s"(u_fl));
       PBN_PSTAMP(k, 0);
       if (k >= 1) {
         // ---- state part of step t = k - 1
@@ -1987,10 +2108,7 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
           rs[w] = slot[(2 * W + w) * 64 + lane];
         }
         info = slot[3 * W * 64 + lane];
-        if (valid && (u_fl & 1u)) {
-#pragma unroll
-          for (int w = 0; w < W; ++w) LANE_ST(a.obs, t * plane + (size_t)w * n, le, (size_t)n_steps * plane, 7, st[w]);
-        }
+        store_obs(st);
 #pragma unroll
         for (int w = 0; w < W; ++w) Sg[32 * w + l32] = lane_transpose32(s1[w], lane);
         __builtin_amdgcn_wave_barrier();
@@ -2045,7 +2163,7 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
 #pragma unroll
         for (int w = 0; w < W; ++w) sp[w] = lane_transpose32(X[w], lane);
         PBN_PSTAMP_AT(k, 13);
-        finish(t, sp, s1, gam, rs, info);
+        finish((u_fl & 8u) != 0, sp, s1, gam, rs, info);
       }
       PBN_PSTAMP(k, 1);
       lds_barrier();
