@@ -62,6 +62,40 @@ __host__ __device__ __forceinline__ Word4 philox(uint32_t c0, uint32_t c1, uint3
   return Word4{c0, c1, c2, c3};
 }
 
+// The key schedule of philox<R> on its own: rk0[r], rk1[r] = the keys of round r (k + r * Weyl
+// constant, modulo 2^32).  It depends on the seed alone, so a loop that draws every step builds it
+// once in front of the loop instead of once per call (pbn_rollout_pipe's RNG waves).
+template <int R = kPhiloxRounds>
+__host__ __device__ __forceinline__ void philox_round_keys(uint32_t k0, uint32_t k1, uint32_t (&rk0)[R],
+                                                            uint32_t (&rk1)[R]) {
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    rk0[r] = k0;
+    rk1[r] = k1;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+}
+
+// philox<R, XM> with the round keys of philox_round_keys given: the same round function, no key
+// bump inside
+template <int R = kPhiloxRounds, uint32_t XM = 0u>
+__host__ __device__ __forceinline__ Word4 philox_rk(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+                                                     const uint32_t (&rk0)[R], const uint32_t (&rk1)[R]) {
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = xor3((uint32_t)(p1 >> 32), c1, r == R - 1 ? (rk0[r] ^ XM) : rk0[r]);
+    const uint32_t n2 = xor3((uint32_t)(p0 >> 32), c3, r == R - 1 ? (rk1[r] ^ XM) : rk1[r]);
+    c1 = (uint32_t)p1;
+    c3 = (uint32_t)p0;
+    c0 = n0;
+    c2 = n2;
+  }
+  return Word4{c0, c1, c2, c3};
+}
+
 __host__ __device__ __forceinline__ Word4 draw(uint64_t seed, uint64_t id, uint64_t step,
                                                 uint32_t stream, uint32_t idx) {
   return philox((uint32_t)id, (uint32_t)step, (stream << 28) | (idx & 0x0FFFFFFFu),

@@ -1410,6 +1410,15 @@ __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
+// The running 64-bit step of an RNG wave's loop, held as its two words (wave-uniform: an SGPR
+// pair) and advanced by one: the low word wraps and the high word takes the carry, as
+// a.step + k does.  Written as the two instructions: the compiler would rebuild the sum from
+// a.step and the loop counter every step, and turn hi << 16 (counter word 3's step half: the
+// shift drops bits 48 and up, as the law's & 0xFFFF does) into a 64-bit shift and a mask.
+__device__ __forceinline__ void step_advance(uint32_t& lo, uint32_t& hi) {
+  asm("s_add_u32 %0, %0, 1\n\ts_addc_u32 %1, %1, 0" : "+s"(lo), "+s"(hi) : : "scc");
+}
+
 // ------------------------------- rollout kernel, three waves per pair of 32-env groups
 // Block = two groups (64 envs; lanes 32h..32h+31 of every wave work on group 2*block + h).
 // The step splits into work that depends only on the counter-based RNG and work that
@@ -1605,16 +1614,24 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
     const uint32_t n1 = (uint32_t)(N + 1);
     const uint32_t* att_words = L + a.att_off + u_na + 1;
     const uint2* lut = reinterpret_cast<const uint2*>(L + a.gap_lut_off);
-    auto env_call = [&](int k) {
-      const uint64_t step = a.step + (uint64_t)k;
-      const uint32_t ge_hi = (uint32_t)((ge >> 32) & 0xFFFFu) | ((uint32_t)((step >> 32) & 0xFFFFu) << 16);
-      return pbn::philox((uint32_t)ge, (uint32_t)step, pbn::kStreamEnv << 28, ge_hi, u_k0, u_k1);
+    // the Philox key schedule, built once per wave (pinned: opaque SGPR values that are not
+    // rematerialised as adds of literals in the loop), and the running step of the ENV call being
+    // computed, one ahead of the step being drawn: advanced by one per step, its low word wraps
+    // and its high half carries as a.step + k does; the shift drops bits 48 and up
+    uint32_t rk0[pbn::kPhiloxRounds], rk1[pbn::kPhiloxRounds];
+    pbn::philox_round_keys(k0, k1, rk0, rk1);
+#pragma unroll
+    for (int r = 0; r < pbn::kPhiloxRounds; ++r) asm volatile("" : "+s"(rk0[r]), "+s"(rk1[r]));
+    const uint32_t ge_h16 = (uint32_t)((ge >> 32) & 0xFFFFu);
+    uint32_t step_lo = (uint32_t)a.step, step_hi = (uint32_t)(a.step >> 32);
+    auto env_call = [&]() {
+      return pbn::philox_rk((uint32_t)ge, step_lo, pbn::kStreamEnv << 28, ge_h16 | (step_hi << 16), rk0, rk1);
     };
     StepRows<uint32_t> fm_rows = rows_open(a.flipmask, n, (size_t)n_steps * plane);
     // one step (k < n_steps; `odd` = k & 1, known at compile time: the slot costs no select):
     // this step's draws from E, the next step's ENV call into E_next
     auto env_step = [&](int k, auto odd, const Word4& E, Word4& E_next) {
-      asm volatile("" : "+s"(u_k0), "+s"(u_k1), "+s"(u_gx), "+s"(u_na), "+s"(u_mnf));
+      asm volatile("" : "+s"(u_gx), "+s"(u_na), "+s"(u_mnf));
       asm volatile("" : "+s"(u_hb), "+s"(u_hp), "+s"(u_hz), "+s"(u_fl));
       PBN_ISA_LOOP("env_fast", W);
       PBN_PSTAMP(k, 0);
@@ -1637,7 +1654,8 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
         asm volatile("" ::: "memory");   // the LDS reads above are issued here
         __builtin_amdgcn_sched_barrier(0);
         PBN_PSTAMP_AT(k, 16);
-        E_next = env_call(k + 1);   // (one unused call per launch)
+        step_advance(step_lo, step_hi);
+        E_next = env_call();   // (one unused call per launch)
         asm volatile("" : "+v"(E_next.x), "+v"(E_next.y), "+v"(E_next.z), "+v"(E_next.w));
         __builtin_amdgcn_sched_barrier(0);
         PBN_PSTAMP_AT(k, 17);
@@ -1679,13 +1697,14 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
         for (int w = 0; w < W; ++w) rows_store(fm_rows, w, (size_t)w * n, le, valid, 8, m[w]);
         rows_advance(fm_rows, plane);
         if (p2 < N - 1) {   // rare: a fourth flip is possible (gap k >= 3: PERT call (k-3)>>2, word (k-3)&3)
-          const uint64_t step = a.step + (uint64_t)k;
-          const uint32_t ge_hi = (uint32_t)((ge >> 32) & 0xFFFFu) | ((uint32_t)((step >> 32) & 0xFFFFu) << 16);
+          // this step's words: the running step is one ahead (a borrow where its low word wrapped)
+          const uint32_t step_lo_k = step_lo - 1u, step_hi_k = step_hi - (step_lo == 0u ? 1u : 0u);
+          const uint32_t ge_hi = ge_h16 | (step_hi_k << 16);
           Word4 P = E;
           int pos = p2;
           for (int kk = 3; pos < N - 1; ++kk) {
             if (((kk - 3) & 3) == 0)
-              P = pbn::philox((uint32_t)ge, (uint32_t)step, (pbn::kStreamPert << 28) | (uint32_t)((kk - 3) >> 2), ge_hi, u_k0, u_k1);
+              P = pbn::philox_rk((uint32_t)ge, step_lo_k, (pbn::kStreamPert << 28) | (uint32_t)((kk - 3) >> 2), ge_hi, rk0, rk1);
             const int j4 = (kk - 3) & 3;
             const uint32_t u = j4 == 0 ? P.x : (j4 == 1 ? P.y : (j4 == 2 ? P.z : P.w));
             pos += gap_lut(lut, a.gap_shift, a.gap_nb, u);
@@ -1706,7 +1725,7 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
     };
     // two steps per trip with the ENV words alternating between EA and EB: no copies between
     // steps; the block's last barrier (the state wave's step n_steps - 1) follows the loop
-    Word4 EA = env_call(0), EB = EA;
+    Word4 EA = env_call(), EB = EA;
     for (int k = 0; k < n_steps; k += 2) {
       env_step(k, std::false_type{}, EA, EB);
       if (k + 1 < n_steps) env_step(k + 1, std::true_type{}, EB, EA);
@@ -1838,23 +1857,29 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
       constexpr int NQ = decltype(nq_c)::value;   // thresholds per node: max_nf - 1
       const uint32_t* cmi = cm + l32 * sel_mask_stride(B);
       uint32_t* lt_base = slots + (3 * W + 1) * 64 + half * 32 * W + l32;
-      auto sel_calls = [&](int k, uint32_t (&d)[16]) {
-        const uint64_t step = a.step + (uint64_t)k;
-        const uint32_t G_hi = (uint32_t)((G >> 32) & 0xFFFFu) | ((uint32_t)((step >> 32) & 0xFFFFu) << 16);
+      // the key schedule and the running step of the calls being computed, as in env_fast
+      uint32_t rk0[pbn::kPhiloxRounds], rk1[pbn::kPhiloxRounds];
+      pbn::philox_round_keys(k0, k1, rk0, rk1);
+#pragma unroll
+      for (int r = 0; r < pbn::kPhiloxRounds; ++r) asm volatile("" : "+s"(rk0[r]), "+s"(rk1[r]));
+      const uint32_t G_h16 = (uint32_t)((G >> 32) & 0xFFFFu);
+      uint32_t step_lo = (uint32_t)a.step, step_hi = (uint32_t)(a.step >> 32);
+      auto sel_calls = [&](uint32_t (&d)[16]) {
+        const uint32_t G_hi = G_h16 | (step_hi << 16);
 #pragma unroll
         for (int c = 0; c < CPN; ++c) {
-          const Word4 o = pbn::philox((uint32_t)G, (uint32_t)step, (pbn::kStreamSel << 28) | (uint32_t)(4 * l32 + c),
-                                             G_hi, u_k0, u_k1);
+          const Word4 o = pbn::philox_rk((uint32_t)G, step_lo, (pbn::kStreamSel << 28) | (uint32_t)(4 * l32 + c),
+                                         G_hi, rk0, rk1);
           d[4 * c + 0] = o.x; d[4 * c + 1] = o.y; d[4 * c + 2] = o.z; d[4 * c + 3] = o.w;
         }
       };
       // one step: this step's compares from `cur`, the next step's calls into `nxt`
       auto sel_step = [&](int k, auto odd, const uint32_t (&cur)[16], uint32_t (&nxt)[16]) {
-        asm volatile("" : "+s"(u_k0), "+s"(u_k1));
         PBN_ISA_LOOP("sel_fast", NQ);
         PBN_PSTAMP(k, 0);
         {
-          sel_calls(k + 1, nxt);   // (one unused set per launch)
+          step_advance(step_lo, step_hi);
+          sel_calls(nxt);   // (one unused set per launch)
 #ifdef PBN_STAMPS
 #pragma unroll
           for (int d = 0; d < 16; ++d) asm volatile("" : "+v"(nxt[d]));
@@ -1876,7 +1901,7 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
       uint32_t dA[16], dB[16];
 #pragma unroll
       for (int d = 0; d < 16; ++d) { dA[d] = 0; dB[d] = 0; }
-      sel_calls(0, dA);
+      sel_calls(dA);
       for (int k = 0; k < n_steps; k += 2) {
         sel_step(k, std::false_type{}, dA, dB);
         if (k + 1 < n_steps) sel_step(k + 1, std::true_type{}, dB, dA);
