@@ -92,8 +92,8 @@ StepFn pick_pipe(int W, int B, bool many) {
   });
 }
 
-using ResetFn = void (*)(const int32_t*, const uint32_t*, int, int, int, uint64_t, uint64_t, uint64_t, int64_t,
-                         uint32_t*, uint8_t*, uint8_t*);
+using ResetFn = void (*)(const int32_t*, const uint32_t*, int, int, int, uint32_t, uint64_t, uint64_t, uint64_t,
+                         int64_t, uint32_t*, uint8_t*, uint8_t*);
 ResetFn pick_reset(int W) {
   switch (W) {
     case 1: return pbn_reset_kernel<1>;
@@ -429,7 +429,8 @@ int pbn_reset(pbn_net* net, uint64_t seed, uint64_t step, uint64_t env_offset, i
   const unsigned blocks = (unsigned)((n_envs + threads - 1) / threads);
   const StepArgs& b = net->base;
   hipLaunchKernelGGL(net->reset, dim3(blocks), dim3(threads), 0, (hipStream_t)stream, b.att_start, b.att_states,
-                     b.n_attr, b.n_states, b.n_nodes, seed, step, env_offset, n_envs, d_state, d_target, d_t);
+                     b.n_attr, b.n_states, b.n_nodes, b.am1_magic, seed, step, env_offset, n_envs, d_state, d_target,
+                     d_t);
   HIP_OK(hipGetLastError());
   return PBN_OK;
 }

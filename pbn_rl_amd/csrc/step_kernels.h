@@ -2,6 +2,9 @@
 // kernels and their helpers (library-internal).  Included by pbn_env.hip (host side, the
 // one-update instances) and pbn_settle.hip (the settle-law instances), so the two halves of
 // the template instances compile in parallel.
+// The per-env half of the transition law (ext64 and the bounded draws, the perturbation mask, the
+// step's outcome: oracle/pbn_oracle.c's ext64, reset_draw, gap_of and step epilogue) is stated once,
+// in step_law.h, the device statement of that law; the kernels here read and write memory around it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,9 +18,10 @@
 #include "bitslice.h"
 #include "net_layout.h"
 #include "philox.h"
+#include "step_law.h"
 
-using pbn::bfi;
-using pbn::Word4;
+using pbn::bfi, pbn::Word4;
+using pbn::actions_from_draw, pbn::actions_mask31, pbn::ext64, pbn::valid_word_mask;   // (step_law.h)
 
 namespace {
 
@@ -332,21 +336,6 @@ __device__ __forceinline__ void rows_store(const StepRows<T>& r, int w, size_t w
 // written back
 // (r05_u: 495 -> 49 MB written per 20-step launch at config 2, +1 % on the settle line)
 #define LANE_STV(base, idx, len, site, v) ((base)[CK((idx), (len), (site))] = (v))
-__device__ __forceinline__ uint32_t valid_word_mask(int n, int w) {
-  const int bits = n - 32 * w;
-  return bits >= 32 ? 0xFFFFFFFFu : (bits <= 0 ? 0u : ((1u << bits) - 1u));
-}
-
-// One bounded draw from the 64-bit uniform X = (hi:lo), keeping the rest of X: v =
-// floor(X * K / 2^64) in [0, K), X <- X * K mod 2^64 (two v_mad_u64_u32; bias <= K / 2^64;
-// oracle/pbn_oracle.c ext64).
-__device__ __forceinline__ uint32_t ext64(uint32_t& hi, uint32_t& lo, uint32_t K) {
-  const uint64_t x = (uint64_t)lo * K;
-  const uint64_t y = (uint64_t)hi * K + (x >> 32);
-  lo = (uint32_t)x;
-  hi = (uint32_t)y;
-  return (uint32_t)(y >> 32);
-}
 
 // The LDS table image from global memory, all of a thread's loads issued before its stores
 // (four loads in flight per thread, where a load-store loop waits once per element)
@@ -391,37 +380,6 @@ __device__ __forceinline__ int hash_probe(const uint32_t* __restrict__ htab, uin
 #pragma unroll
   for (int w = 0; w < W; ++w) eq = eq && ent[w] == sp[w];
   return eq ? (int)ent[W] : -1;
-}
-
-// Three actions uniform on [0, N]: the base-(N+1) digits of c, one draw over (N+1)^3.
-// Division by N+1 is a multiply-high by magic = ceil(2^32 / (N+1)), exact for c * (N+1) < 2^32
-// (c < (N+1)^3 <= 129^3).
-template <int W>
-__device__ __forceinline__ void actions_from_draw(uint32_t c, int N, uint32_t magic, uint32_t (&m)[W]) {
-  const uint32_t n1 = (uint32_t)(N + 1);
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {   // action a in [0, N]: 0 = no-op, else flip node a-1
-    const uint32_t qt = __umulhi(c, magic);
-    const int act = (int)(c - qt * n1);
-    c = qt;
-#pragma unroll
-    for (int w = 0; w < W; ++w)
-      if (act > 0 && ((act - 1) >> 5) == w) m[w] |= 1u << ((act - 1) & 31);
-  }
-}
-
-// actions_from_draw for one word with N <= 31: action a sets bit a - 1 as 1 << (a - 1), where
-// a = 0 shifts by 31 (the shift count's low five bits) onto a bit past the network that `vmask`
-// (valid_word_mask(N, 0)) clears once for all three: no per-action guard
-__device__ __forceinline__ uint32_t actions_mask31(uint32_t c, uint32_t n1, uint32_t magic, uint32_t vmask) {
-  uint32_t m = 0;
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const uint32_t qt = __umulhi(c, magic);
-    m |= 1u << ((c - qt * n1 - 1u) & 31u);
-    c = qt;
-  }
-  return m & vmask;
 }
 
 // gap(u) = min{m in 1..N : u < C[m-1]} (N+1 or more if none); C padded with 0xFFFFFFFF.
@@ -722,6 +680,20 @@ __device__ __forceinline__ int gap_any(int mode, const uint32_t* __restrict__ L,
   return mode ? gap_of(L, a.cdf_len, u) : gap_est(L, a.cdf_len, a.inv_log2q, u);
 }
 
+// an update's first three gaps, which are independent: computed side by side by one method
+__device__ __forceinline__ void first_gaps(int mode, const uint32_t* __restrict__ L, const StepArgs& a, uint32_t u0,
+                                           uint32_t u1, uint32_t u2, int& g0, int& g1, int& g2) {
+  if (mode == 2) {
+    g0 = gap_any(2, L, a, u0); g1 = gap_any(2, L, a, u1); g2 = gap_any(2, L, a, u2);
+  } else if (mode) {
+    g0 = gap_of(L, a.cdf_len, u0); g1 = gap_of(L, a.cdf_len, u1); g2 = gap_of(L, a.cdf_len, u2);
+  } else {
+    g0 = gap_est(L, a.cdf_len, a.inv_log2q, u0);
+    g1 = gap_est(L, a.cdf_len, a.inv_log2q, u1);
+    g2 = gap_est(L, a.cdf_len, a.inv_log2q, u2);
+  }
+}
+
 // (u < c_q) for the wave-uniform threshold classes: one bit-sliced comparison per class with
 // SGPR digit masks, then a per-lane pick by class index (record .y)
 template <int B>
@@ -751,13 +723,6 @@ __device__ __forceinline__ pbn::Word4 upper_to_lower(pbn::Word4 v) {
   const auto b1 = __builtin_amdgcn_permlane32_swap(v.z, v.w, false, false);
   const auto b2 = __builtin_amdgcn_permlane32_swap(b1[1], b1[0], false, false);
   return pbn::Word4{a2[0], a2[1], b2[0], b2[1]};
-}
-
-template <int W>
-__device__ __forceinline__ void set_bit(uint32_t (&g)[W], int pos, int N) {
-#pragma unroll
-  for (int w = 0; w < W; ++w)
-    if ((unsigned)pos < (unsigned)N && (pos >> 5) == w) g[w] |= 1u << (pos & 31);
 }
 
 // attractor id of the per-env state sp (open-addressing LDS hash; keys are unique, so the probe
@@ -989,9 +954,9 @@ __device__ __forceinline__ void node_update_settle(const StepArgs& a, const uint
 
 // The settle law (settle_max >= 2, include/pbn_env.h "Step law"): updates k = 1 ..
 // settle_max - 1 of the envs (lower lanes) whose state sp is outside every attractor, until all
-// of the wave's envs are in one.  Update k: perturbation gaps j = 0, 1, ... from SETTLE_ENV call
-// ((k-1) << 8 | j >> 2), word j & 3 (per env); unperturbed envs take the rule update with their
-// own SETTLE_SEL uniforms of update k (node_update_settle).  Returns true on lanes whose env is
+// of the wave's envs are in one.  Update k: perturbation gaps j = 0, 1, ... from the SETTLE_ENV
+// stream (pbn::gap_tail, per env); unperturbed envs take the rule update with their own
+// SETTLE_SEL uniforms of update k (node_update_settle).  Returns true on lanes whose env is
 // still outside after the last update (PBN_FLAG_UNSETTLED).
 template <int W, int B>
 __device__ __forceinline__ bool settle_updates(const StepArgs& a, const uint32_t* __restrict__ L, uint32_t* S,
@@ -1007,22 +972,15 @@ __device__ __forceinline__ bool settle_updates(const StepArgs& a, const uint32_t
   bool open = live && att < 0;   // (envs past n_envs take part in the transposes only)
   for (int k = 1; k < a.settle_max; ++k) {
     if (__ballot(open) == 0) return false;
-    const uint32_t sub = (uint32_t)(k - 1);
     uint32_t gam[W];
     bool pk = false;
 #pragma unroll
     for (int w = 0; w < W; ++w) gam[w] = 0;
-    if (open) {
-      Word4 P = {0, 0, 0, 0};
-      int pos = -1;
-      for (int j = 0; pos < N - 1; ++j) {
-        if ((j & 3) == 0)
-          P = pbn::philox(ge_lo, st_lo, (pbn::kStreamSettleEnv << 28) | (sub << 8) | (uint32_t)(j >> 2), ge_hi, k0, k1);
-        const int j4 = j & 3;
-        const uint32_t u = j4 == 0 ? P.x : (j4 == 1 ? P.y : (j4 == 2 ? P.z : P.w));
-        pos += gap_any(a.gap_exact, L, a, u);
-        set_bit<W>(gam, pos, N);
-      }
+    if (open) {   // every gap of the update through the tail: from word 0, position -1
+      pbn::gap_tail<W>(
+          (uint32_t)k, 0, -1, N, Word4{0, 0, 0, 0},
+          [&](int jj) { return pbn::philox(ge_lo, st_lo, pbn::gap_call_c2((uint32_t)k, jj), ge_hi, k0, k1); },
+          [&](uint32_t u) { return gap_any(a.gap_exact, L, a, u); }, gam);
 #pragma unroll
       for (int w = 0; w < W; ++w) pk = pk || gam[w] != 0;
     }
@@ -1076,7 +1034,6 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) pbn_step_wave(StepArgs a)
   // each wave's S planes
   uint32_t* L = smem;
   uint32_t* S = smem + a.tab_words + (size_t)wv * a.wave_words;
-  const uint32_t* cdf = L;
   const float* rtab = reinterpret_cast<const float*>(L + a.cdf_len);
   const uint32_t* htab = L + a.cdf_len + 4 * (N + 1);
   const int64_t n = a.n_envs;
@@ -1231,17 +1188,10 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) pbn_step_wave(StepArgs a)
     const uint32_t c_act = ext64(xhi, xlo, n1 * n1 * n1);
     if (a.n_attr >= 1) {
       const int32_t* att_first = reinterpret_cast<const int32_t*>(L + a.att_off);
-      const uint32_t A = (uint32_t)a.n_attr;
-      uint32_t as = 0;
-      if (A >= 2) {
-        const uint32_t c = ext64(xhi, xlo, A * (A - 1));
-        as = a.am1_magic ? __umulhi(c, a.am1_magic) : c;   // c / (A - 1)
-        r_nt = c - as * (A - 1);
-        r_nt += (r_nt >= as) ? 1u : 0u;
-      }
-      // (single-state attractors: the draw over one state is 0 and state a is attractor a's)
-      const int st0 = a.att_single ? (int)as : att_first[as];
-      r_row = (uint32_t)st0 + (a.att_single ? 0u : ext64(xhi, xlo, (uint32_t)(att_first[as + 1] - st0)));
+      uint32_t as;
+      uint64_t xr = 0;   // (u2 is taken from the chain here)
+      pbn::pair_draw(xhi, xlo, (uint32_t)a.n_attr, a.am1_magic, as, r_nt);
+      r_row = pbn::start_pick(xhi, xlo, as, a.att_single != 0, [&](uint32_t i) { return att_first[i]; }, xr);
     }
     u2 = xhi;
     if (random_actions) {
@@ -1264,31 +1214,13 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) pbn_step_wave(StepArgs a)
     // perturbation positions are prefix sums of geometric gaps; the first three gaps
     // (u = E.x, E.y, u2) are independent, so they are computed side by side
     int g0, g1, g2;
-    if (a.gap_exact == 2) {
-      g0 = gap_any(2, L, a, E.x); g1 = gap_any(2, L, a, E.y); g2 = gap_any(2, L, a, u2);
-    } else if (a.gap_exact) {
-      g0 = gap_of(cdf, a.cdf_len, E.x); g1 = gap_of(cdf, a.cdf_len, E.y); g2 = gap_of(cdf, a.cdf_len, u2);
-    } else {
-      g0 = gap_est(cdf, a.cdf_len, a.inv_log2q, E.x);
-      g1 = gap_est(cdf, a.cdf_len, a.inv_log2q, E.y);
-      g2 = gap_est(cdf, a.cdf_len, a.inv_log2q, u2);
-    }
-    const int p0 = g0 - 1, p1 = p0 + g1, p2 = p1 + g2;
-    set_bit<W>(gam, p0, N);
-    set_bit<W>(gam, p1, N);
-    set_bit<W>(gam, p2, N);
-    if (p2 < N - 1) {   // rare: a fourth flip is possible (gap k >= 3: PERT call (k-3)>>2, word (k-3)&3)
-      Word4 P = E;
-      int pos = p2;
-      for (int kk = 3; pos < N - 1; ++kk) {
-        if (((kk - 3) & 3) == 0)
-          P = pbn::philox(ge_lo, st_lo, (pbn::kStreamPert << 28) | (uint32_t)((kk - 3) >> 2), ge_hi, kk0, kk1);
-        const int j4 = (kk - 3) & 3;
-        const uint32_t u = j4 == 0 ? P.x : (j4 == 1 ? P.y : (j4 == 2 ? P.z : P.w));
-        pos += gap_any(a.gap_exact, L, a, u);
-        set_bit<W>(gam, pos, N);
-      }
-    }
+    first_gaps(a.gap_exact, L, a, E.x, E.y, u2, g0, g1, g2);
+    const int p2 = pbn::first_gaps_mask<W>(g0, g1, g2, N, gam);
+    if (p2 < N - 1)   // rare: a fourth flip is possible
+      pbn::gap_tail<W>(
+          0u, 3, p2, N, E,
+          [&](int jj) { return pbn::philox(ge_lo, st_lo, pbn::gap_call_c2(0, jj), ge_hi, kk0, kk1); },
+          [&](uint32_t u) { return gap_any(a.gap_exact, L, a, u); }, gam);
 #pragma unroll
     for (int w = 0; w < W; ++w) pert = pert || gam[w] != 0;
   }
@@ -1347,44 +1279,30 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) pbn_step_wave(StepArgs a)
         if (k < a.r_k) a.r_action[CK((size_t)rj * a.r_k + k, (size_t)a.r_cap * a.r_k, 42)] = rav[k];
     }
   }
-  const bool in_attr = att >= 0;
-  const bool term = in_attr && (uint32_t)att == tg0;
-  const bool wrong = in_attr && !term;
-  int tt = (int)tt0 + 1;
-  tt = tt > 255 ? 255 : tt;
-  const bool trunc = a.horizon > 0 && tt >= a.horizon;
-  const float rwd = rtab[(int)pc * 4 + 2 * (int)term + (int)wrong];
+  const pbn::StepOutcome o = pbn::step_outcome(att, tg0, tt0, a.horizon, (a.mode & PBN_MODE_AUTORESET) != 0, pert,
+                                               unsettled);
+  const float rwd = rtab[(int)pc * 4 + pbn::reward_slot(o)];
   a.reward[CK(ks * n + le, n_steps * n, 11)] = rwd;
-  uint32_t fl = (uint32_t)term | ((uint32_t)trunc << 1) | ((uint32_t)in_attr << 2) | ((uint32_t)pert << 3) |
-                ((uint32_t)unsettled << 5);
-  if ((a.mode & PBN_MODE_AUTORESET) && (term || trunc)) {
-    uint32_t nt;
+  if (o.reset) {
     if (a.n_attr >= 1) {   // the attractor draws of step 2 (attractor states from the LDS image)
       const uint32_t* att_words = L + a.att_off + a.n_attr + 1;
 #pragma unroll
       for (int w = 0; w < W; ++w) sp[w] = att_words[(size_t)r_row * W + w];
-      nt = r_nt;
+      tg0 = r_nt;
     } else {
-      const Word4 rr = pbn::philox(ge_lo, st_lo, (pbn::kStreamReset << 28) | 1u, ge_hi, kk0, kk1);
-      const uint32_t rw4[4] = {rr.x, rr.y, rr.z, rr.w};
-#pragma unroll
-      for (int w = 0; w < W; ++w) sp[w] = rw4[w] & valid_word_mask(N, w);
-      nt = PBN_NO_TARGET;
+      tg0 = pbn::random_reset_state<W>(ge_lo, st_lo, ge_hi, kk0, kk1, N, sp);
     }
-    tg0 = nt;
-    tt = 0;
-    fl |= PBN_FLAG_RESET;
   }
-  a.flags[CK(ks * n + le, n_steps * n, 15)] = (uint8_t)fl;
+  a.flags[CK(ks * n + le, n_steps * n, 15)] = (uint8_t)o.flags;
   if constexpr (!SETTLE) {
     if (a.r_state) {   // done as pbn_replay_store derives it from the flags byte
-      const uint8_t d = a.r_done_mask ? ((fl & a.r_done_mask) ? 1 : 0) : ((uint8_t)fl ? 1 : 0);
+      const uint8_t d = a.r_done_mask ? ((o.flags & a.r_done_mask) ? 1 : 0) : ((uint8_t)o.flags ? 1 : 0);
       a.r_reward[CK(rj, a.r_cap, 45)] = rwd;
       a.r_done[CK(rj, a.r_cap, 46)] = d;
       if (a.r_done_out) a.r_done_out[CK(le, n, 47)] = d;
     }
   }
-  tt0 = (uint32_t)tt;
+  tt0 = o.t;
 #pragma unroll
   for (int w = 0; w < W; ++w) st[w] = sp[w];
   }  // live
@@ -1555,7 +1473,6 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
   // LDS: table image | S planes [2][32W] | two slots
   //   slot = m[W][64] | gam[W][64] | rs[W][64] | info[64] | lt[LQ][2][32W]
   uint32_t* L = smem;
-  const uint32_t* cdf = L;
   const float* rtab = reinterpret_cast<const float*>(L + a.cdf_len);
   const uint32_t* htab = L + a.cdf_len + 4 * (N + 1);
   const uint4* selq = reinterpret_cast<const uint4*>(L + a.sel_off);
@@ -1641,11 +1558,11 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
         uint32_t xhi = E.w, xlo = E.z;
         const uint32_t c_act = ext64(xhi, xlo, n1 * n1 * n1);
         const uint32_t u2 = (uint32_t)((((((uint64_t)E.w) << 32) | E.z) * a.x_mult) >> 32);
-        const uint32_t c = ext64(xhi, xlo, A * (A - 1));
-        const uint32_t as = a.am1_magic ? __umulhi(c, a.am1_magic) : c;   // c / (A - 1)
+        const uint32_t c = ext64(xhi, xlo, A * (A - 1));   // pair_draw (A >= 2), its halves apart
+        const uint32_t as = pbn::pair_start(c, a.am1_magic);
         uint32_t rs[W];
 #pragma unroll
-        for (int w = 0; w < W; ++w) rs[w] = att_words[(size_t)as * W + w];
+        for (int w = 0; w < W; ++w) rs[w] = att_words[(size_t)as * W + w];   // (att_single: start_pick is `as`)
         const uint2 e0 = lut[min(E.x >> a.gap_shift, (uint32_t)a.gap_nb)];
         const uint2 e1 = lut[min(E.y >> a.gap_shift, (uint32_t)a.gap_nb)];
         const uint2 e2 = lut[min(u2 >> a.gap_shift, (uint32_t)a.gap_nb)];
@@ -1660,8 +1577,7 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
         __builtin_amdgcn_sched_barrier(0);
         PBN_PSTAMP_AT(k, 17);
         // part 3: the rest of step k's draws
-        uint32_t rt = c - as * (A - 1);
-        rt += (rt >= as) ? 1u : 0u;
+        const uint32_t rt = pbn::pair_target(c, as, A);
         uint32_t m[W], gam[W];
 #pragma unroll
         for (int w = 0; w < W; ++w) { m[w] = 0; gam[w] = 0; }
@@ -1673,17 +1589,9 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
         const int g0 = (int)e0.y + (E.x >= e0.x ? 1 : 0);   // gap_lut
         const int g1 = (int)e1.y + (E.y >= e1.x ? 1 : 0);
         const int g2 = (int)e2.y + (u2 >= e2.x ? 1 : 0);
-        const int p0 = g0 - 1, p1 = p0 + g1, p2 = p1 + g2;
-        if constexpr (W == 1) {
-          // N <= 31: a position past the network lands on a bit >= N (bit 31 at most), cleared by
-          // the word mask once
-          gam[0] = ((1u << min((uint32_t)p0, 31u)) | (1u << min((uint32_t)p1, 31u)) |
-                    (1u << min((uint32_t)p2, 31u))) & valid_word_mask(N, 0);
-        } else {
-          set_bit<W>(gam, p0, N);
-          set_bit<W>(gam, p1, N);
-          set_bit<W>(gam, p2, N);
-        }
+        int p2;
+        if constexpr (W == 1) p2 = pbn::first_gaps_mask31(g0, g1, g2, valid_word_mask(N, 0), gam[0]);   // N <= 31
+        else p2 = pbn::first_gaps_mask<W>(g0, g1, g2, N, gam);
         bool pert = false;
 #pragma unroll
         for (int w = 0; w < W; ++w) {
@@ -1696,20 +1604,14 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
 #pragma unroll
         for (int w = 0; w < W; ++w) rows_store(fm_rows, w, (size_t)w * n, le, valid, 8, m[w]);
         rows_advance(fm_rows, plane);
-        if (p2 < N - 1) {   // rare: a fourth flip is possible (gap k >= 3: PERT call (k-3)>>2, word (k-3)&3)
+        if (p2 < N - 1) {   // rare: a fourth flip is possible
           // this step's words: the running step is one ahead (a borrow where its low word wrapped)
           const uint32_t step_lo_k = step_lo - 1u, step_hi_k = step_hi - (step_lo == 0u ? 1u : 0u);
           const uint32_t ge_hi = ge_h16 | (step_hi_k << 16);
-          Word4 P = E;
-          int pos = p2;
-          for (int kk = 3; pos < N - 1; ++kk) {
-            if (((kk - 3) & 3) == 0)
-              P = pbn::philox_rk((uint32_t)ge, step_lo_k, (pbn::kStreamPert << 28) | (uint32_t)((kk - 3) >> 2), ge_hi, rk0, rk1);
-            const int j4 = (kk - 3) & 3;
-            const uint32_t u = j4 == 0 ? P.x : (j4 == 1 ? P.y : (j4 == 2 ? P.z : P.w));
-            pos += gap_lut(lut, a.gap_shift, a.gap_nb, u);
-            set_bit<W>(gam, pos, N);
-          }
+          pbn::gap_tail<W>(
+              0u, 3, p2, N, E,
+              [&](int jj) { return pbn::philox_rk((uint32_t)ge, step_lo_k, pbn::gap_call_c2(0, jj), ge_hi, rk0, rk1); },
+              [&](uint32_t u) { return gap_lut(lut, a.gap_shift, a.gap_nb, u); }, gam);
           pert = false;
 #pragma unroll
           for (int w = 0; w < W; ++w) {
@@ -1768,31 +1670,14 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
           if (u_na >= 1) {
             const int32_t* att_first = reinterpret_cast<const int32_t*>(L + a.att_off);
             const uint32_t* att_words = L + a.att_off + u_na + 1;
-            const uint32_t A = (uint32_t)u_na;
-            uint32_t as = 0;
-            rt = 0;
-            if (A >= 2) {
-              const uint32_t c = ext64(xhi, xlo, A * (A - 1));
-              as = a.am1_magic ? __umulhi(c, a.am1_magic) : c;   // c / (A - 1)
-              rt = c - as * (A - 1);
-              rt += (rt >= as) ? 1u : 0u;
-            }
-            // (single-state attractors: the draw over one state is 0 and state a is attractor a's)
-            const int st0 = (u_fl & 16u) ? (int)as : att_first[as];
-            uint32_t idx = 0;
-            if (!(u_fl & 16u)) {
-              const uint32_t size = (uint32_t)(att_first[as + 1] - st0);
-              idx = ext64(xhi, xlo, size);
-              xr *= size;
-            }
+            uint32_t as;
+            pbn::pair_draw(xhi, xlo, (uint32_t)u_na, a.am1_magic, as, rt);
+            const uint32_t row = pbn::start_pick(xhi, xlo, as, (u_fl & 16u) != 0,
+                                                 [&](uint32_t i) { return att_first[i]; }, xr);
 #pragma unroll
-            for (int w = 0; w < W; ++w) rs[w] = att_words[(size_t)(st0 + idx) * W + w];
+            for (int w = 0; w < W; ++w) rs[w] = att_words[(size_t)row * W + w];
           } else {
-            const Word4 rr = pbn::philox(ge_lo, st_lo, (pbn::kStreamReset << 28) | 1u, ge_hi, u_k0, u_k1);
-            const uint32_t rw4[4] = {rr.x, rr.y, rr.z, rr.w};
-#pragma unroll
-            for (int w = 0; w < W; ++w) rs[w] = rw4[w] & valid_word_mask(N, w);
-            rt = PBN_NO_TARGET;
+            rt = pbn::random_reset_state<W>(ge_lo, st_lo, ge_hi, u_k0, u_k1, N, rs);
           }
           const uint32_t u2 = (uint32_t)(xr >> 32);   // = xhi
           if (u_fl & 4u) {
@@ -1808,31 +1693,13 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
 #pragma unroll
           for (int w = 0; w < W; ++w) pc += __builtin_popcount(m[w]);
           int g0, g1, g2;
-          if (u_gx == 2) {
-            g0 = gap_any(2, L, a, E.x); g1 = gap_any(2, L, a, E.y); g2 = gap_any(2, L, a, u2);
-          } else if (u_gx) {
-            g0 = gap_of(cdf, a.cdf_len, E.x); g1 = gap_of(cdf, a.cdf_len, E.y); g2 = gap_of(cdf, a.cdf_len, u2);
-          } else {
-            g0 = gap_est(cdf, a.cdf_len, a.inv_log2q, E.x);
-            g1 = gap_est(cdf, a.cdf_len, a.inv_log2q, E.y);
-            g2 = gap_est(cdf, a.cdf_len, a.inv_log2q, u2);
-          }
-          const int p0 = g0 - 1, p1 = p0 + g1, p2 = p1 + g2;
-          set_bit<W>(gam, p0, N);
-          set_bit<W>(gam, p1, N);
-          set_bit<W>(gam, p2, N);
-          if (p2 < N - 1) {   // rare: a fourth flip is possible (gap k >= 3: PERT call (k-3)>>2, word (k-3)&3)
-            Word4 P = E;
-            int pos = p2;
-            for (int kk = 3; pos < N - 1; ++kk) {
-              if (((kk - 3) & 3) == 0)
-                P = pbn::philox(ge_lo, st_lo, (pbn::kStreamPert << 28) | (uint32_t)((kk - 3) >> 2), ge_hi, u_k0, u_k1);
-              const int j4 = (kk - 3) & 3;
-              const uint32_t u = j4 == 0 ? P.x : (j4 == 1 ? P.y : (j4 == 2 ? P.z : P.w));
-              pos += gap_any(u_gx, L, a, u);
-              set_bit<W>(gam, pos, N);
-            }
-          }
+          first_gaps(u_gx, L, a, E.x, E.y, u2, g0, g1, g2);
+          const int p2 = pbn::first_gaps_mask<W>(g0, g1, g2, N, gam);
+          if (p2 < N - 1)   // rare: a fourth flip is possible
+            pbn::gap_tail<W>(
+                0u, 3, p2, N, E,
+                [&](int jj) { return pbn::philox(ge_lo, st_lo, pbn::gap_call_c2(0, jj), ge_hi, u_k0, u_k1); },
+                [&](uint32_t u) { return gap_any(u_gx, L, a, u); }, gam);
           bool pert = false;
 #pragma unroll
           for (int w = 0; w < W; ++w) pert = pert || gam[w] != 0;
@@ -2016,6 +1883,8 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
             }
           }
         }
+        // (pbn::step_outcome restated, the horizon test as a value: through the helper the state
+        // wave's epilogue gains a scalar instruction)
         const bool in_attr = att >= 0;
         const bool term = in_attr && (uint32_t)att == tg0;
         const bool wrong = in_attr && !term;
@@ -2435,8 +2304,8 @@ pbn_rollout_settle(StepArgs a) {
       // gap 2's uniform (X * x_mult, off the draws' chain)
       uint32_t xhi = E.w, xlo = E.z;
       const uint32_t c_act = ext64(xhi, xlo, n1 * n1 * n1);
-      const uint32_t c = ext64(xhi, xlo, A * (A - 1));
-      const uint32_t as = a.am1_magic ? __umulhi(c, a.am1_magic) : c;   // c / (A - 1)
+      const uint32_t c = ext64(xhi, xlo, A * (A - 1));   // pair_draw (A >= 2), its halves apart
+      const uint32_t as = pbn::pair_start(c, a.am1_magic);
       const uint32_t u2 = first ? (uint32_t)((((((uint64_t)E.w) << 32) | E.z) * a.x_mult) >> 32) : E.z;
       uint32_t rs[W];
 #pragma unroll
@@ -2444,8 +2313,7 @@ pbn_rollout_settle(StepArgs a) {
       const uint2 e0 = lut[min(E.x >> a.gap_shift, (uint32_t)a.gap_nb)];
       const uint2 e1 = lut[min(E.y >> a.gap_shift, (uint32_t)a.gap_nb)];
       const uint2 e2 = lut[min(u2 >> a.gap_shift, (uint32_t)a.gap_nb)];
-      uint32_t rt = c - as * (A - 1);
-      rt += (rt >= as) ? 1u : 0u;
+      const uint32_t rt = pbn::pair_target(c, as, A);
       uint32_t m[W], gam[W];
 #pragma unroll
       for (int w = 0; w < W; ++w) { m[w] = 0; gam[w] = 0; }
@@ -2460,33 +2328,14 @@ pbn_rollout_settle(StepArgs a) {
       const int g0 = (int)e0.y + (E.x >= e0.x ? 1 : 0);   // gap_lut
       const int g1 = (int)e1.y + (E.y >= e1.x ? 1 : 0);
       const int g2 = (int)e2.y + (u2 >= e2.x ? 1 : 0);
-      const int p0 = g0 - 1, p1 = p0 + g1, p2 = p1 + g2;
-      if constexpr (W == 1) {
-        // N <= 31: a position past the network lands on a bit >= N (bit 31 at most), cleared by
-        // the word mask once
-        gam[0] = ((1u << min((uint32_t)p0, 31u)) | (1u << min((uint32_t)p1, 31u)) |
-                  (1u << min((uint32_t)p2, 31u))) & valid_word_mask(N, 0);
-      } else {
-        set_bit<W>(gam, p0, N);
-        set_bit<W>(gam, p1, N);
-        set_bit<W>(gam, p2, N);
-      }
-      if (live && p2 < N - 1) {   // rare: more gaps (k = 0: PERT call (j-3) >> 2, word (j-3) & 3;
-                                  // k >= 1: gap 3 is word 3, gap j >= 4 SETTLE_ENV call (k-1) << 8 | j >> 2)
-        Word4 P = E;
-        int pos = p2;
-        for (int j = 3; pos < N - 1; ++j) {
-          const int jj = first ? j - 3 : j;
-          if ((jj & 3) == 0)
-            P = pbn::philox(ge_lo, st_lo,
-                            first ? ((pbn::kStreamPert << 28) | (uint32_t)(jj >> 2))
-                                  : ((pbn::kStreamSettleEnv << 28) | ((k - 1) << 8) | (uint32_t)(jj >> 2)),
-                            ge_hi, u_k0, u_k1);
-          const int j4 = jj & 3;
-          const uint32_t u = j4 == 0 ? P.x : (j4 == 1 ? P.y : (j4 == 2 ? P.z : P.w));
-          pos += gap_lut(lut, a.gap_shift, a.gap_nb, u);
-          set_bit<W>(gam, pos, N);
-        }
+      int p2;
+      if constexpr (W == 1) p2 = pbn::first_gaps_mask31(g0, g1, g2, valid_word_mask(N, 0), gam[0]);   // N <= 31
+      else p2 = pbn::first_gaps_mask<W>(g0, g1, g2, N, gam);
+      if (live && p2 < N - 1) {   // rare: more gaps (k >= 1: gap 3 is the call's word 3)
+        pbn::gap_tail<W>(
+            k, 3, p2, N, E,
+            [&](int jj) { return pbn::philox(ge_lo, st_lo, pbn::gap_call_c2(k, jj), ge_hi, u_k0, u_k1); },
+            [&](uint32_t u) { return gap_lut(lut, a.gap_shift, a.gap_nb, u); }, gam);
       }
       if (live && first && t < base + R) {   // (an update past the ring is not applied: no row)
         uint32_t* row = stg + (size_t)(t % R) * RW;
@@ -2540,30 +2389,14 @@ pbn_rollout_settle(StepArgs a) {
           if (a.n_attr >= 1) {
             const int32_t* att_first = reinterpret_cast<const int32_t*>(L + a.att_off);
             const uint32_t* att_words = L + a.att_off + a.n_attr + 1;
-            const uint32_t A = (uint32_t)a.n_attr;
-            uint32_t as = 0;
-            rtv = 0;
-            if (A >= 2) {
-              const uint32_t c = ext64(xhi, xlo, A * (A - 1));
-              as = a.am1_magic ? __umulhi(c, a.am1_magic) : c;
-              rtv = c - as * (A - 1);
-              rtv += (rtv >= as) ? 1u : 0u;
-            }
-            const int st0 = a.att_single ? (int)as : att_first[as];
-            uint32_t idx = 0;
-            if (!a.att_single) {
-              const uint32_t size = (uint32_t)(att_first[as + 1] - st0);
-              idx = ext64(xhi, xlo, size);
-              xr *= size;
-            }
+            uint32_t as;
+            pbn::pair_draw(xhi, xlo, (uint32_t)a.n_attr, a.am1_magic, as, rtv);
+            const uint32_t row = pbn::start_pick(xhi, xlo, as, a.att_single != 0,
+                                                 [&](uint32_t i) { return att_first[i]; }, xr);
 #pragma unroll
-            for (int w = 0; w < W; ++w) rs[w] = att_words[(size_t)(st0 + idx) * W + w];
+            for (int w = 0; w < W; ++w) rs[w] = att_words[(size_t)row * W + w];
           } else {
-            const Word4 rr = pbn::philox(ge_lo, st_lo, (pbn::kStreamReset << 28) | 1u, ge_hi, u_k0, u_k1);
-            const uint32_t rw4[4] = {rr.x, rr.y, rr.z, rr.w};
-#pragma unroll
-            for (int w = 0; w < W; ++w) rs[w] = rw4[w] & valid_word_mask(N, w);
-            rtv = PBN_NO_TARGET;
+            rtv = pbn::random_reset_state<W>(ge_lo, st_lo, ge_hi, u_k0, u_k1, N, rs);
           }
           u2 = (uint32_t)(xr >> 32);
           if (u_fl & 4u) {
@@ -2588,37 +2421,13 @@ pbn_rollout_settle(StepArgs a) {
         }
         // gaps 0, 1 = words 0, 1; gap 2 = u2 (k = 0) or word 2 (k >= 1); then, rarely, more
         int g0, g1, g2;
-        if (a.gap_exact == 2) {   // the bucket table (every kaban network): three reads side by side
-          const uint2* lut = reinterpret_cast<const uint2*>(L + a.gap_lut_off);
-          g0 = gap_lut(lut, a.gap_shift, a.gap_nb, E.x);
-          g1 = gap_lut(lut, a.gap_shift, a.gap_nb, E.y);
-          g2 = gap_lut(lut, a.gap_shift, a.gap_nb, u2);
-        } else {
-          g0 = gap_any(a.gap_exact, L, a, E.x);
-          g1 = gap_any(a.gap_exact, L, a, E.y);
-          g2 = gap_any(a.gap_exact, L, a, u2);
-        }
-        const int p0 = g0 - 1, p1 = p0 + g1, p2 = p1 + g2;
-        set_bit<W>(gam, p0, N);
-        set_bit<W>(gam, p1, N);
-        set_bit<W>(gam, p2, N);
-        if (p2 < N - 1) {   // k = 0: gap j >= 3 is PERT call (j-3) >> 2, word (j-3) & 3;
-                            // k >= 1: gap 3 is word 3, gap j >= 4 SETTLE_ENV call (k-1) << 8 | j >> 2
-          Word4 P = E;
-          int pos = p2;
-          for (int j = 3; pos < N - 1; ++j) {
-            const int jj = first ? j - 3 : j;
-            if ((jj & 3) == 0)
-              P = pbn::philox(ge_lo, st_lo,
-                              first ? ((pbn::kStreamPert << 28) | (uint32_t)(jj >> 2))
-                                    : ((pbn::kStreamSettleEnv << 28) | ((k - 1) << 8) | (uint32_t)(jj >> 2)),
-                              ge_hi, u_k0, u_k1);
-            const int j4 = jj & 3;
-            const uint32_t u = j4 == 0 ? P.x : (j4 == 1 ? P.y : (j4 == 2 ? P.z : P.w));
-            pos += gap_any(a.gap_exact, L, a, u);
-            set_bit<W>(gam, pos, N);
-          }
-        }
+        first_gaps(a.gap_exact, L, a, E.x, E.y, u2, g0, g1, g2);
+        const int p2 = pbn::first_gaps_mask<W>(g0, g1, g2, N, gam);
+        if (p2 < N - 1)   // rare: more gaps (k >= 1: gap 3 is the call's word 3)
+          pbn::gap_tail<W>(
+              k, 3, p2, N, E,
+              [&](int jj) { return pbn::philox(ge_lo, st_lo, pbn::gap_call_c2(k, jj), ge_hi, u_k0, u_k1); },
+              [&](uint32_t u) { return gap_any(a.gap_exact, L, a, u); }, gam);
       }
       PBN_PSTAMP_AT(it - kSettleStampIt + 10, 17);
 #pragma unroll
@@ -2818,6 +2627,7 @@ pbn_rollout_settle(StepArgs a) {
 #pragma unroll
         for (int w = 0; w < W; ++w) row[kSF + w * 64 + lane] = cur[w];
         reinterpret_cast<uint16_t*>(row + kSU)[lane] = (uint16_t)min(k + 1, 0xFFFFu);
+        // (pbn::step_outcome restated: through the helper this loop's epilogue changes its listing)
         const bool in_attr = att >= 0;
         const bool term = in_attr && (uint32_t)att == tg0;
         const bool wrong = in_attr && !term;
@@ -2894,39 +2704,28 @@ __global__ void __launch_bounds__(256) pbn_hist_kernel(const uint32_t* __restric
 template <int W>
 __global__ void __launch_bounds__(256) pbn_reset_kernel(const int32_t* __restrict__ att_start,
                                                         const uint32_t* __restrict__ att_states,
-                                                        int n_attr, int n_states, int N, uint64_t seed, uint64_t step,
-                                                        uint64_t env_offset, int64_t n, uint32_t* state,
-                                                        uint8_t* target, uint8_t* t) {
+                                                        int n_attr, int n_states, int N, uint32_t am1_magic,
+                                                        uint64_t seed, uint64_t step, uint64_t env_offset, int64_t n,
+                                                        uint32_t* state, uint8_t* target, uint8_t* t) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint64_t ge = env_offset + (uint64_t)i;
-  const Word4 r0 = pbn::draw(seed, ge, step, pbn::kStreamReset, 0);
   uint32_t ns[W];
   uint32_t nt;
   if (n_attr >= 1) {
-    // (start, target != start) in one draw over the A(A-1) pairs, then the start state
-    // uniformly within the start attractor, from the 64-bit value (word 1 : word 0)
-    uint32_t hi = r0.y, lo = r0.x;
-    const uint32_t A = (uint32_t)n_attr;
-    uint32_t as = 0;
-    nt = 0;
-    if (A >= 2) {
-      const uint32_t c = ext64(hi, lo, A * (A - 1));
-      as = c / (A - 1);
-      nt = c - as * (A - 1);
-      nt += (nt >= as) ? 1u : 0u;
-    }
-    const int st0 = att_start[CK(as, n_attr + 1, 20)];
-    const uint32_t size = (uint32_t)(att_start[CK(as + 1, n_attr + 1, 21)] - st0);
-    const uint32_t idx = ext64(hi, lo, size);
+    // the pair and the start state from the 64-bit value (word 1 : word 0) of RESET call 0
+    const Word4 r0 = pbn::draw(seed, ge, step, pbn::kStreamReset, 0);
+    uint32_t hi = r0.y, lo = r0.x, as;
+    uint64_t xr = 0;   // (nothing is drawn after the start state)
+    pbn::pair_draw(hi, lo, (uint32_t)n_attr, am1_magic, as, nt);
+    const uint32_t row = pbn::start_pick(hi, lo, as, false,
+                                         [&](uint32_t j) { return att_start[CK(j, n_attr + 1, 20)]; }, xr);
 #pragma unroll
-    for (int w = 0; w < W; ++w) ns[w] = att_states[CK((size_t)(st0 + idx) * W + w, (size_t)n_states * W, 22)];
+    for (int w = 0; w < W; ++w) ns[w] = att_states[CK((size_t)row * W + w, (size_t)n_states * W, 22)];
   } else {
-    const Word4 r1 = pbn::draw(seed, ge, step, pbn::kStreamReset, 1);
-    const uint32_t rw[4] = {r1.x, r1.y, r1.z, r1.w};
-#pragma unroll
-    for (int w = 0; w < W; ++w) ns[w] = rw[w] & valid_word_mask(N, w);
-    nt = PBN_NO_TARGET;
+    nt = pbn::random_reset_state<W>((uint32_t)ge, (uint32_t)step,
+                                    (uint32_t)((ge >> 32) & 0xFFFFu) | ((uint32_t)((step >> 32) & 0xFFFFu) << 16),
+                                    (uint32_t)seed, (uint32_t)(seed >> 32), N, ns);
   }
 #pragma unroll
   for (int w = 0; w < W; ++w) state[(size_t)w * n + i] = ns[w];

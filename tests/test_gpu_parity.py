@@ -19,7 +19,7 @@ from pbn_rl_amd.network import load_network
 from pbn_rl_amd.spec import EnvSpec
 from pbn_rl_amd.vector_env import VectorPBNEnv
 
-from .synthetic import random_spec
+from .synthetic import LAW_BRANCHES, law_branch_specs, random_spec
 
 pytestmark = pytest.mark.gpu
 
@@ -356,3 +356,39 @@ def test_step_ragged_env_counts(name, settle):
                       out.data_ptr(), None, rew.data_ptr(), fl.data_ptr(), None) == -22   # offset not a multiple of 32
     assert L.pbn_rollout(h, seed, 0, 0, 33, 1, 0, st.data_ptr(), fm.data_ptr(), tg.data_ptr(), tt.data_ptr(), None,
                          None, rew.data_ptr(), fl.data_ptr(), None) == -22   # rollouts keep whole groups
+
+
+# ------------------------------------------------ the branches of the per-env law, per caller
+# Which test reaches each branch of csrc/step_law.h's helpers through each caller (the callers are
+# chosen by PBN_ROLL, the step law and the network).  "branches" is test_law_branches_* below and
+# test_gpu_settle.py's test_settle_law_branches_*; a dash is a cell the routing cannot reach (the
+# fast env loops take only nets with two or more single-state attractors, the bucket table and
+# random actions; pbn_reset has no gaps, masks or outcome).
+#
+# caller            | n_attr 0 / 1 / >= 2                  | multi-state | gap_exact 0 / 1 / 2                    | given masks / random        | tail taken                   | autoreset off        | horizon 0
+# wave one-step     | no_attractors_autoreset / branches / step_matches_oracle | branches | branches / from_random_states_no_perturbation / step_matches_oracle | step_matches_oracle modes 0-3 | high_perturbation_multi_flip_path | step_matches_oracle mode 0, 2 | from_random_states_no_perturbation
+# wave lean rollout | rollout_high_perturbation_and_no_attractors / branches / rollout_matches_oracle | branches | branches / branches / rollout_matches_oracle | rollout_matches_oracle mode 1 / 3 | rollout_high_perturbation_and_no_attractors | branches | branches
+# wave settle       | branches / branches / settle_step_matches_oracle | branches | branches / settle_pipe_caps (p = 0, lean: branches) / settle_step_matches_oracle | settle_step_matches_oracle mode 0 / 3 | settle_unsettled_flag_and_high_perturbation | settle_step_matches_oracle mode 0 | branches
+# pipe general      | rollout_high_perturbation_and_no_attractors / branches / rollout_matches_oracle mode 1 | branches | branches / branches / rollout_matches_oracle mode 1 | rollout_matches_oracle mode 1 / branches | branches | branches | branches
+# pipe env_fast     | - / - / rollout_matches_oracle mode 3 | -           | - / - / rollout_matches_oracle mode 3   | - / rollout_matches_oracle  | rollout_high_perturbation_and_no_attractors, branches (fast_tail_*) | - (random actions with autoreset off: branches) | branches
+# settle general    | branches / branches / settle_rollout_matches_oracle mode 1 | branches | branches / settle_pipe_caps_and_odd_groups / settle_rollout mode 1 | settle_rollout mode 1 / branches | branches | branches | branches
+# settle env_fast   | - / - / settle_rollout_matches_oracle mode 3 | -    | - / - / settle_rollout mode 3           | - / settle_rollout mode 3   | settle_unsettled_flag... (W = 2), branches (fast_tail_*) | branches | branches
+# reset             | no_attractors_autoreset / branches / every test | branches | -                               | -                           | -                            | -                    | -
+@pytest.mark.parametrize("case", LAW_BRANCHES)
+def test_law_branches_step(case):
+    """pbn_step (the wave kernel's one-step variant) on the nets of law_branch_specs: given masks
+    without autoreset and without a horizon, then random actions with autoreset."""
+    run_pair(law_branch_specs(horizon=0)[case], 96, 4, mode=0, start_random=True)
+    run_pair(law_branch_specs(horizon=3)[case], 96, 5, mode=3, env_offset=64)
+
+
+@pytest.mark.parametrize("variant", ["pipe", "lean"])
+@pytest.mark.parametrize("case", LAW_BRANCHES)
+def test_law_branches_rollout(case, variant, monkeypatch):
+    """pbn_rollout through the pipelined kernel (its general env loop for every case but
+    the fast_tail cases in random-action mode, which take env_fast) and the wave kernel's lean variant:
+    96 envs (three groups: the pipelined kernel's last block is half empty)."""
+    monkeypatch.setenv("PBN_ROLL", variant)
+    run_rollout_pair(law_branch_specs(horizon=3)[case], 96, 5, 3)   # random actions, autoreset
+    run_rollout_pair(law_branch_specs(horizon=0)[case], 96, 4, 2)   # random actions, no autoreset, no horizon
+    run_rollout_pair(law_branch_specs(horizon=3)[case], 96, 4, 1)   # given masks

@@ -23,7 +23,7 @@ from pbn_rl_amd.spec import EnvSpec
 from pbn_rl_amd.vector_env import VectorPBNEnv
 
 from .protocol import load_agent, replay, summary
-from .synthetic import random_spec
+from .synthetic import LAW_BRANCHES, law_branch_specs, random_spec
 from .test_bn_pin import reference_result
 from .oracle_env import OracleVectorEnv
 from .test_gpu_parity import run_pair, run_rollout_pair, u32
@@ -219,3 +219,25 @@ def test_settle_unpacked_threshold_compare():
     run_rollout_pair(spec, 2080, 8, 3)
     run_rollout_pair(spec, 1024, 5, 1)
     run_pair(spec, 2048, 4, mode=3, env_offset=1024)
+
+
+# (the table of callers and branches: tests/test_gpu_parity.py, above test_law_branches_step)
+@pytest.mark.parametrize("variant", ["auto", "lean"])
+@pytest.mark.parametrize("case", LAW_BRANCHES)
+def test_settle_law_branches_step(case, variant, monkeypatch):
+    """pbn_step under the settle law on the nets of law_branch_specs: the pipelined settle
+    kernel's one-step launch (auto; 96 envs are whole groups) and the wave kernel's variant 3."""
+    monkeypatch.setenv("PBN_ROLL", variant)
+    run_pair(law_branch_specs(horizon=0, settle=4)[case], 96, 4, mode=0, start_random=True)
+    run_pair(law_branch_specs(horizon=3, settle=4)[case], 96, 5, mode=3, env_offset=64)
+
+
+@pytest.mark.parametrize("variant", ["pipe", "lean"])
+@pytest.mark.parametrize("case", LAW_BRANCHES)
+def test_settle_law_branches_rollout(case, variant, monkeypatch):
+    """pbn_rollout under the settle law: pbn_rollout_settle's general env loop (env_fast for
+    the fast_tail cases in random-action mode) and the wave kernel's variant 4, 96 envs."""
+    monkeypatch.setenv("PBN_ROLL", variant)
+    run_rollout_pair(law_branch_specs(horizon=3, settle=4)[case], 96, 5, 3)
+    run_rollout_pair(law_branch_specs(horizon=0, settle=4)[case], 96, 4, 2)
+    run_rollout_pair(law_branch_specs(horizon=3, settle=4)[case], 96, 4, 1)
