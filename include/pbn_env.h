@@ -784,6 +784,32 @@ int pbn_ddqn_schedule(double* d_beta, double beta_increment, const int64_t* d_st
                       int64_t target_update, float* d_target_params, const float* d_params, int64_t n_params,
                       float* d_target_image, const float* d_image, int64_t n_image, void* stream);
 
+/*
+ * pbn_rollout_dqn: pbn_rollout_ex with a DQN choosing every action inside the launch (the policy
+ * rollout).  An additive export (the ABI version is unchanged).  Before step k of the launch the
+ * wave that owns an env runs pbn_dqn_flipmask_from_state's forward on the env's current state and
+ * target id (the ones step k - 1 left, an autoreset's new target included), takes the first maximum
+ * of Q and applies the EXPLORE law at (seed, env_offset + env, step + k): explore iff word 0 <
+ * floor(epsilon * 2^32), then a = (word 1 * (N + 1)) >> 32.  The action's flip mask is the step's
+ * intervention; from there the step is pbn_rollout_ex's.  The actions, flip masks and every other
+ * output equal those of n_steps rounds of pbn_dqn_flipmask_from_state followed by pbn_step, bit
+ * for bit, under either step law.
+ *   d_image      pbn_dqn_pack's image of the network (h0, h1), 16-byte aligned
+ *   d_flipmask   out [n_steps][W][n]: the flip masks of the actions taken
+ *   d_actions    out [n_steps][n] int32, nullable
+ *   mode         PBN_MODE_AUTORESET or 0; PBN_MODE_RANDOM_ACTIONS is rejected
+ * Preconditions and the other buffers as pbn_rollout_ex: whole 32-env groups, the state stepped in
+ * place, every element of every given buffer written; n_steps == 0 or n_envs == 0 is a successful
+ * no-op.  Shapes as pbn_dqn_pack (N + 1 <= 128, hidden widths 1..64); epsilon in [0, 1].  Every
+ * argument error returns PBN_EINVAL before any device call.
+ */
+int pbn_rollout_dqn(pbn_net* net, uint64_t seed, uint64_t step, uint64_t env_offset, int64_t n_envs,
+                    int32_t n_steps, uint32_t mode, uint32_t* d_state, uint8_t* d_target, uint8_t* d_t,
+                    int32_t h0, int32_t h1, const float* d_image, float epsilon,
+                    uint32_t* d_flipmask /* out [n_steps][W][n] */, int32_t* d_actions /* out [n_steps][n], nullable */,
+                    uint32_t* d_obs, uint32_t* d_final_state, float* d_reward, uint8_t* d_flags,
+                    uint16_t* d_updates, void* stream);
+
 const char* pbn_last_error(void);
 int pbn_abi_version(void);
 

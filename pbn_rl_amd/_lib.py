@@ -33,7 +33,7 @@ EXPORTS = ["pbn_net_create", "pbn_net_destroy", "pbn_net_words", "pbn_reset", "p
            "pbn_eval_track", "pbn_eval_reduce", "pbn_per_store", "pbn_per_sample", "pbn_per_update",
            "pbn_bdq_td_loss_per", "pbn_bdq_learn_per", "pbn_dqn_layout", "pbn_dqn_image_floats", "pbn_dqn_pack",
            "pbn_dqn_flipmask_from_state", "pbn_ddqn_learn_workspace", "pbn_ddqn_learn", "pbn_ddqn_schedule",
-           "pbn_last_error",
+           "pbn_rollout_dqn", "pbn_last_error",
            "pbn_abi_version"]
 SOURCES = ["pbn_env.hip", "pbn_settle.hip", "pbn_agent.hip", "pbn_qnet.hip", "pbn_learn.hip", "pbn_eval.hip",
            "pbn_per.hip", "pbn_ddqn.hip"]
@@ -225,6 +225,10 @@ def load() -> ctypes.CDLL:
     if hasattr(L, "pbn_ddqn_schedule"):   # (additive export of ABI 11: the captured DDQN frame's schedule step)
         L.pbn_ddqn_schedule.argtypes = [vp, ctypes.c_double, vp, i64, i64, vp, vp, i64, vp, vp, i64, vp]
         L.pbn_ddqn_schedule.restype = ctypes.c_int
+    if hasattr(L, "pbn_rollout_dqn"):   # (additive export of ABI 11: the policy rollout)
+        L.pbn_rollout_dqn.argtypes = [vp, u64, u64, u64, i64, i32, u32, vp, vp, vp, i32, i32, vp, f32, vp, vp, vp, vp,
+                                      vp, vp, vp, vp]
+        L.pbn_rollout_dqn.restype = ctypes.c_int
     L.pbn_abi_version.argtypes = []
     L.pbn_abi_version.restype = ctypes.c_int
     _lib = L

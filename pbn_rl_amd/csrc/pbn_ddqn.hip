@@ -39,83 +39,16 @@
 #include <algorithm>
 
 #include "../../include/pbn_env.h"
+#include "dqn_forward.h"
 #include "net_view.h"
 #include "philox.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+// (Dims, make_dims, forward16 and the argmax: dqn_forward.h, shared with the policy rollout)
 
-constexpr int kMaxHT = 4;       // hidden widths <= 64: at most four 16-wide tiles
-constexpr int kMaxA = 128;      // N + 1 <= 128
 constexpr int kActWaves = 4;
 constexpr int kGradThreads = 256;
-
-enum Seg { BIL_W, BIL_B, L1_W, L1_B, OUT_W, OUT_B, TOTAL };
-
-inline int64_t al16(int64_t x) { return (x + 15) & ~int64_t(15); }
-
-// Shapes, the parameter layout (pbn_dqn_layout) and the image layout.  Image (floats):
-//   T     [n_attr][N][H0p]   the bilinear layer contracted with each attractor's first state,
-//                            zero past h0 (a row without a target reads none of it)
-//   b0 [H0p], b1 [H1p], b2 [Ap]   the biases, zero-padded
-//   w1f   [H1p/16][H0p/16][64][4]  linears.0: lane 16g + r holds W[16 ot + r][16 kt + 4g + v]
-//   w1b   [H1p/16][H0p/16][64][4]  its transpose's operand: W[16 ot + 4g + v][16 kt + r]
-//   w2f   [Ap/16][H1p/16][64][4]   output, as w1f
-struct Dims {
-  int N, W, n_attr, h0, h1, A, H0p, H1p, Ap, H0T, H1T, AT;
-  int64_t off[TOTAL + 1], sz[TOTAL];
-  int64_t iT, ib0, ib1, ib2, iw1f, iw1b, iw2f, itotal;
-};
-
-const char* shape_error(int N, int h0, int h1) {
-  if (N < 1 || N + 1 > kMaxA) return "n_nodes must be 1..127 (N + 1 <= 128 actions)";
-  if (h0 < 1 || h0 > 64 || h1 < 1 || h1 > 64) return "hidden widths must be 1..64";
-  return nullptr;
-}
-
-void make_dims(int N, int W, int n_attr, int h0, int h1, Dims* d) {
-  d->N = N;
-  d->W = W;
-  d->n_attr = n_attr;
-  d->h0 = h0;
-  d->h1 = h1;
-  d->A = N + 1;
-  d->H0T = (h0 + 15) / 16;
-  d->H1T = (h1 + 15) / 16;
-  d->AT = (N + 1 + 15) / 16;
-  d->H0p = 16 * d->H0T;
-  d->H1p = 16 * d->H1T;
-  d->Ap = 16 * d->AT;
-  const int64_t sz[TOTAL] = {(int64_t)h0 * N * N, h0, (int64_t)h1 * h0, h1, (int64_t)d->A * h1, d->A};
-  int64_t o = 0;
-  for (int s = 0; s < TOTAL; ++s) {
-    d->sz[s] = sz[s];
-    d->off[s] = o;
-    o += al16(sz[s]);
-  }
-  d->off[TOTAL] = o;
-  int64_t i = 0;
-  d->iT = i;
-  i += (int64_t)n_attr * N * d->H0p;
-  d->ib0 = i;
-  i += d->H0p;
-  d->ib1 = i;
-  i += d->H1p;
-  d->ib2 = i;
-  i += d->Ap;
-  d->iw1f = i;
-  i += (int64_t)d->H1p * d->H0p;
-  d->iw1b = i;
-  i += (int64_t)d->H1p * d->H0p;
-  d->iw2f = i;
-  i += (int64_t)d->Ap * d->H1p;
-  d->itotal = i;
-}
-
-__device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 // ---- the image -------------------------------------------------------------------------------
 // Element e of the image of parameters P.  A table entry adds its weights by ascending j.
@@ -151,119 +84,6 @@ __global__ void __launch_bounds__(256) dqn_pack_kernel(Dims d, const float* __re
                                                         const uint32_t* __restrict__ att_first, float* __restrict__ img) {
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < d.itotal; e += (int64_t)gridDim.x * 256)
     img[e] = image_value(d, P, att_first, e);
-}
-
-// ---- the forward of 16 rows on one wave --------------------------------------------------------
-// Lane 16g + r works on row r.  sw: the row's state words (bits past N cleared), t: its target id.
-// y0[kb] / y1[kb] hold features 16 kb + 4g + v of row r after the ReLU (zero in the padding);
-// qf(at, q) receives Q[16 at + 4g + v][r] tile by tile, at ascending.
-template <class QF>
-__device__ __forceinline__ void forward16(const Dims& d, const float* __restrict__ img, const uint32_t (&sw)[4], int t,
-                                          int lane, float4 (&y0)[kMaxHT], float4 (&y1)[kMaxHT], QF&& qf) {
-  const int g = lane >> 4;
-  // bilinear layer: bias + the table rows of the set bits, i ascending
-#pragma unroll
-  for (int kb = 0; kb < kMaxHT; ++kb)
-    y0[kb] = kb < d.H0T ? *reinterpret_cast<const float4*>(img + d.ib0 + 16 * kb + 4 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
-  if (t < d.n_attr) {
-    const float* T = img + d.iT + (int64_t)t * d.N * d.H0p + 4 * g;
-    // four set bits a round: their table rows are requested together (one round trip, not four)
-    // and added in order; a slot past the last bit reads row 0 and adds zeros
-    for (int w = 0; w < d.W; ++w) {
-      uint32_t x = sw[w];
-      while (x) {
-        float4 tv[4][kMaxHT];
-        bool on[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          on[u] = x != 0u;
-          const int i = on[u] ? 32 * w + __builtin_ctz(x) : 0;
-          x &= x - 1u;
-          const float* row = T + (int64_t)i * d.H0p;
-#pragma unroll
-          for (int kb = 0; kb < kMaxHT; ++kb)
-            if (kb < d.H0T) tv[u][kb] = *reinterpret_cast<const float4*>(row + 16 * kb);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-#pragma unroll
-          for (int kb = 0; kb < kMaxHT; ++kb)
-            if (kb < d.H0T) {
-              y0[kb].x += on[u] ? tv[u][kb].x : 0.f;
-              y0[kb].y += on[u] ? tv[u][kb].y : 0.f;
-              y0[kb].z += on[u] ? tv[u][kb].z : 0.f;
-              y0[kb].w += on[u] ? tv[u][kb].w : 0.f;
-            }
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int kb = 0; kb < kMaxHT; ++kb) {
-    y0[kb].x = fmaxf(y0[kb].x, 0.f);
-    y0[kb].y = fmaxf(y0[kb].y, 0.f);
-    y0[kb].z = fmaxf(y0[kb].z, 0.f);
-    y0[kb].w = fmaxf(y0[kb].w, 0.f);
-  }
-  // linears.0
-  const float4* w1 = reinterpret_cast<const float4*>(img + d.iw1f) + lane;
-#pragma unroll
-  for (int ot = 0; ot < kMaxHT; ++ot) {
-    y1[ot] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (ot < d.H1T) {
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int kb = 0; kb < kMaxHT; ++kb)
-        if (kb < d.H0T) {
-          const float4 w = w1[(ot * d.H0T + kb) * 64];
-          acc = mfma(w.x, y0[kb].x, acc);
-          acc = mfma(w.y, y0[kb].y, acc);
-          acc = mfma(w.z, y0[kb].z, acc);
-          acc = mfma(w.w, y0[kb].w, acc);
-        }
-      const float4 b = *reinterpret_cast<const float4*>(img + d.ib1 + 16 * ot + 4 * g);
-      y1[ot] = make_float4(fmaxf(acc[0] + b.x, 0.f), fmaxf(acc[1] + b.y, 0.f), fmaxf(acc[2] + b.z, 0.f),
-                           fmaxf(acc[3] + b.w, 0.f));
-    }
-  }
-  // output
-  const float4* w2 = reinterpret_cast<const float4*>(img + d.iw2f) + lane;
-  for (int at = 0; at < d.AT; ++at) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kb = 0; kb < kMaxHT; ++kb)
-      if (kb < d.H1T) {
-        const float4 w = w2[(at * d.H1T + kb) * 64];
-        acc = mfma(w.x, y1[kb].x, acc);
-        acc = mfma(w.y, y1[kb].y, acc);
-        acc = mfma(w.z, y1[kb].z, acc);
-        acc = mfma(w.w, y1[kb].w, acc);
-      }
-    const float4 b = *reinterpret_cast<const float4*>(img + d.ib2 + 16 * at + 4 * g);
-    const f32x4 q = {acc[0] + b.x, acc[1] + b.y, acc[2] + b.z, acc[3] + b.w};
-    qf(at, q);
-  }
-}
-
-// torch.argmax's order: NaN is the maximum, of equals the lower index wins
-__device__ __forceinline__ bool better(float a, int ia, float b, int ib) {
-  if (isnan(a)) return isnan(b) ? ia < ib : true;
-  if (isnan(b)) return false;
-  return a > b || (a == b && ia < ib);
-}
-
-// the first maximum of a row whose lanes (g = 0..3) each hold a running (best, index)
-__device__ __forceinline__ int row_argmax(float best, int bi) {
-#pragma unroll
-  for (int m = 16; m <= 32; m <<= 1) {
-    const float ob = __shfl_xor(best, m);
-    const int oi = __shfl_xor(bi, m);
-    if (better(ob, oi, best, bi)) {
-      best = ob;
-      bi = oi;
-    }
-  }
-  return bi;
 }
 
 __device__ __forceinline__ void load_words(const Dims& d, const uint32_t* __restrict__ st, int64_t stride, int64_t j,
@@ -326,13 +146,13 @@ __global__ void __launch_bounds__(64 * kActWaves) dqn_act_kernel(ActArgs a) {
   uint64_t eps_u = a.eps_u;
   if (a.d_eps) {   // device epsilon: clamped to [0, 1], NaN -> 0
     const float ef = fminf(fmaxf(*a.d_eps, 0.f), 1.f);
-    eps_u = (uint64_t)floor((double)ef * 4294967296.0);
+    eps_u = explore_threshold(ef);
   }
   const int act = (uint64_t)rw.x < eps_u ? (int)__umulhi(rw.y, (uint32_t)d.A) : bi;
   if (a.actions) a.actions[e] = act;
 #pragma unroll
   for (int w = 0; w < 4; ++w)
-    if (w < d.W) a.flipmask[(size_t)w * a.n + e] = (act > 0 && act <= d.N && ((act - 1) >> 5) == w) ? 1u << ((act - 1) & 31) : 0u;
+    if (w < d.W) a.flipmask[(size_t)w * a.n + e] = action_mask_word(act, d.N, w);
 }
 
 // ---- the update --------------------------------------------------------------------------------
@@ -794,7 +614,7 @@ int pbn_dqn_flipmask_from_state(const pbn_net* net, uint64_t seed, uint64_t step
   a.step = step;
   a.env_offset = env_offset;
   // explore iff word 0 < floor(epsilon * 2^32): epsilon = 1 always explores, 0 never
-  a.eps_u = (uint64_t)floor((double)epsilon * 4294967296.0);
+  a.eps_u = explore_threshold(epsilon);
   a.d_step = d_step;
   a.d_eps = d_epsilon;
   a.q = d_q;

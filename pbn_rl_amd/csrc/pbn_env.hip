@@ -42,6 +42,8 @@ namespace pbn {
 void* settle_kernel(int W, int B, int lean);
 // pbn_settle.hip: pbn_rollout_settle<W, B> (pbn_rollout under the settle law, pipelined)
 void* settle_pipe_kernel(int W, int B);
+// pbn_settle.hip: pbn_step_wave<W, B, 4, PolicyArgs> (pbn_rollout_dqn under the settle law)
+void* settle_dqn_kernel(int W, int B);
 }  // namespace pbn
 
 namespace {
@@ -110,6 +112,7 @@ struct pbn_net {
   StepArgs base{};   // the launch arguments fixed at create (fill_args adds the key and the env range)
   DevBuf tab, att_start, att_states, att_first, fcompact, nrec, sthr, sthr_pk;
   StepFn kernels[kNumKernels] = {};   // nullptr: no instance for this net
+  PolicyFn dqn_kernel = nullptr;      // pbn_rollout_dqn: pbn_step_wave<.., PolicyArgs> under the net's step law
   ResetFn reset = nullptr;
   RouteNet route{};
   int device = 0;
@@ -223,6 +226,11 @@ void pick_kernels(const pbn::NetImage& im, pbn_net* net) {
   net->kernels[kWaveSettleLean] = reinterpret_cast<StepFn>(pbn::settle_kernel(W, B, 1));
   net->kernels[kPipe] = pick_pipe(W, B, many);
   if (!many) net->kernels[kPipeSettle] = reinterpret_cast<StepFn>(pbn::settle_pipe_kernel(W, B));
+  net->dqn_kernel = im.settle_max >= 2
+                        ? reinterpret_cast<PolicyFn>(pbn::settle_dqn_kernel(W, B))
+                        : step_kernel_for(W, B, [](auto w, auto b) -> PolicyFn {
+                            return pbn_step_wave<decltype(w)::value, decltype(b)::value, 2, PolicyArgs>;
+                          });
   net->reset = pick_reset(W);
   net->W = W;
   net->slot_words_settle = im.slot_words_settle;
@@ -247,6 +255,10 @@ int raise_lds_limits(const pbn_net& net) {
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
       return fail(PBN_EDEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
   }
+  if (net.dqn_kernel && net.route.lds_wave <= kLdsDeviceBytes &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(net.dqn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)net.route.lds_wave) != hipSuccess)
+    return fail(PBN_EDEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
   return PBN_OK;
 }
 
@@ -609,6 +621,59 @@ int pbn_rollout_ex(pbn_net* net, uint64_t seed, uint64_t step, uint64_t env_offs
                    uint16_t* d_updates, void* stream) {
   return rollout_impl(net, seed, step, env_offset, n_envs, n_steps, mode, d_state, d_flipmask, d_target, d_t, d_obs,
                       d_final_state, d_reward, d_flags, d_updates, nullptr, nullptr, 0, stream);
+}
+
+int pbn_rollout_dqn(pbn_net* net, uint64_t seed, uint64_t step, uint64_t env_offset, int64_t n_envs,
+                    int32_t n_steps, uint32_t mode, uint32_t* d_state, uint8_t* d_target, uint8_t* d_t, int32_t h0,
+                    int32_t h1, const float* d_image, float epsilon, uint32_t* d_flipmask, int32_t* d_actions,
+                    uint32_t* d_obs, uint32_t* d_final_state, float* d_reward, uint8_t* d_flags,
+                    uint16_t* d_updates, void* stream) {
+  // every argument error before any device call, those that need no net first
+  if (mode & ~(PBN_MODE_AUTORESET | PBN_MODE_RANDOM_ACTIONS)) return fail(PBN_EINVAL, "unknown mode bits");
+  if (mode & PBN_MODE_RANDOM_ACTIONS)
+    return fail(PBN_EINVAL, "pbn_rollout_dqn: the policy chooses the actions (mode takes PBN_MODE_AUTORESET only)");
+  if (n_steps < 0) return fail(PBN_EINVAL, "n_steps < 0");
+  if (n_envs < 0) return fail(PBN_EINVAL, "n_envs < 0");
+  if ((n_envs & 31) || (env_offset & 31)) return fail(PBN_EINVAL, "n_envs and env_offset must be multiples of 32");
+  if (n_envs >= ((int64_t)1 << 30)) return fail(PBN_EINVAL, "n_envs must be below 2^30");
+  if (const char* msg = shape_error(1, h0, h1)) return fail(PBN_EINVAL, msg);
+  if (!(epsilon >= 0.f && epsilon <= 1.f)) return fail(PBN_EINVAL, "epsilon must be in [0, 1]");
+  if (!net) return fail(PBN_EINVAL, "null net");
+  if (const char* msg = shape_error(net->base.n_nodes, h0, h1)) return fail(PBN_EINVAL, msg);
+  if (!net->dqn_kernel) return fail(PBN_EINVAL, "pbn_rollout_dqn: no kernel instance for this net");
+  if (n_envs == 0 || n_steps == 0) return PBN_OK;
+  if (!d_state || !d_target || !d_t || !d_image || !d_flipmask || !d_reward || !d_flags)
+    return fail(PBN_EINVAL, "null buffer");
+  if (!aligned16(d_image)) return fail(PBN_EINVAL, "d_image must be 16-byte aligned");
+  if (((uintptr_t)d_state | (uintptr_t)d_flipmask | (uintptr_t)d_actions | (uintptr_t)d_obs |
+       (uintptr_t)d_final_state | (uintptr_t)d_reward) & 3u)
+    return fail(PBN_EINVAL, "32-bit device buffers must be 4-byte aligned");
+  if ((uintptr_t)d_updates & 1u) return fail(PBN_EINVAL, "d_updates must be 2-byte aligned");
+  if (int rc = pbn::check_device(net)) return rc;
+  StepArgs a;
+  fill_args(net, &a, seed, step, env_offset, n_envs);
+  a.state = d_state;
+  a.state_out = d_state;   // in place, as pbn_rollout_ex
+  a.flipmask = d_flipmask;
+  a.target = d_target;
+  a.t = d_t;
+  a.final_state = d_final_state;
+  a.obs = d_obs;
+  a.reward = d_reward;
+  a.flags = d_flags;
+  a.n_steps = n_steps;
+  a.mode = (int)mode;
+  a.updates = d_updates;
+  PolicyArgs p;
+  make_dims(net->base.n_nodes, net->W, net->base.n_attr, h0, h1, &p.d);
+  p.img = d_image;
+  p.eps_u = explore_threshold(epsilon);
+  p.actions = d_actions;
+  const unsigned blocks = (unsigned)((a.n_groups + kWavesPerBlock - 1) / kWavesPerBlock);
+  hipLaunchKernelGGL(net->dqn_kernel, dim3(blocks), dim3(64 * kWavesPerBlock), net->route.lds_wave,
+                     (hipStream_t)stream, a, p);
+  HIP_OK(hipGetLastError());
+  return PBN_OK;
 }
 
 int pbn_rollout_copy(pbn_net* net, uint64_t seed, uint64_t step, uint64_t env_offset, int64_t n_envs,

@@ -16,6 +16,7 @@
 
 #include "../../include/pbn_env.h"
 #include "bitslice.h"
+#include "dqn_forward.h"
 #include "net_layout.h"
 #include "philox.h"
 #include "step_law.h"
@@ -119,6 +120,15 @@ struct StepArgs {
   int64_t r_cap;
   int r_k;
   uint32_t r_done_mask;
+};
+
+// The policy of a policy rollout (pbn_step_wave<W, B, 2 | 4, PolicyArgs>'s second argument): a DQN whose image
+// (pbn_dqn_pack) the wave reads every step, acting epsilon-greedily under the EXPLORE law
+struct PolicyArgs {
+  Dims d;
+  const float* img;
+  uint64_t eps_u;     // explore_threshold(epsilon)
+  int32_t* actions;   // [n_steps][n] the actions taken (nullable)
 };
 
 typedef unsigned int pbn_u32x4 __attribute__((ext_vector_type(4)));
@@ -1013,9 +1023,17 @@ __device__ __forceinline__ bool settle_updates(const StepArgs& a, const uint32_t
 // 2: rollout with invariants recomputed per step (occupancy first; the rollout of networks
 //    with gates, which the pipelined kernel does not run);
 // 3, 4: 1 and 2 under the settle law (settle_max >= 2: settle_updates after the first update).
-template <int W, int B, int VARIANT>
-__global__ void __launch_bounds__(64 * kWavesPerBlock) pbn_step_wave(StepArgs a) {
+// POL: empty, or PolicyArgs (the policy rollout, pbn_rollout_dqn; variants 2 and 4): a second kernel
+// argument, the DQN whose action on the env's current (state, target) is the step's flip mask, a
+// third source beside the in-kernel random actions and a given mask.
+template <class P>
+__device__ __forceinline__ const P& policy_arg(const P& p) { return p; }
+
+template <int W, int B, int VARIANT, class... POL>
+__global__ void __launch_bounds__(64 * kWavesPerBlock) pbn_step_wave(StepArgs a, POL... pol) {
   constexpr bool LEAN = VARIANT == 2 || VARIANT == 4;
+  constexpr bool POLICY = sizeof...(POL) == 1;
+  static_assert(sizeof...(POL) <= 1 && (!POLICY || LEAN), "the policy is evaluated in the multi-step loop");
   constexpr bool SINGLE = VARIANT == 1 || VARIANT == 3;
   constexpr bool SETTLE = VARIANT >= 3;
   constexpr int CPN = SETTLE ? 0 : B / 4;  // group selection calls per node (the settle law's are per env)
@@ -1135,6 +1153,57 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) pbn_step_wave(StepArgs a)
     for (int w = 0; w < W; ++w) a.obs[CK(ks * plane + (size_t)w * n + le, (size_t)n_steps * plane, 7)] = st[w];
   }
 
+  // ---- 0p. the policy's flip mask: Q of the wave's 32 envs in two 16-row passes of dqn_act's
+  // forward (the whole wave: the MFMAs), the argmax, the EXPLORE draw.  The forward reads the
+  // state and the target the step before left in st / tg0, an autoreset's new target included.
+  if constexpr (POLICY) {
+    const PolicyArgs* p = &policy_arg(pol...);
+    const Dims& d = p->d;
+    const int qg = lane >> 4, r16 = lane & 15;
+    int greedy[2];
+#pragma unroll
+    for (int ps = 0; ps < 2; ++ps) {   // lane 16 qg + r16 works on env 16 ps + r16
+      uint32_t sw[4];
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        uint32_t x = w < W ? (uint32_t)__shfl((int)st[w < W ? w : 0], 16 * ps + r16) : 0u;
+        if (w == d.W - 1 && (d.N & 31)) x &= (1u << (d.N & 31)) - 1u;   // (as load_words)
+        sw[w] = x;
+      }
+      const int t = __shfl((int)tg0, 16 * ps + r16);
+      float4 y0[kMaxHT], y1[kMaxHT];
+      float best = -INFINITY;
+      int bi = INT_MAX;
+      // (PRELOAD: the same arithmetic with the dense layers' operands requested early; the wave
+      // has its SIMD to itself, so nothing else hides a round trip)
+      forward16<true>(d, p->img, sw, t, lane, y0, y1, [&](int at, f32x4 q) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const int ai = 16 * at + 4 * qg + v;
+          if (ai < d.A && better(q[v], ai, best, bi)) {
+            best = q[v];
+            bi = ai;
+          }
+        }
+      });
+      greedy[ps] = row_argmax(best, bi);
+    }
+    // env l32's argmax: lane l32 & 15 of pass l32 >> 4
+    const int g0 = __shfl(greedy[0], r16), g1 = __shfl(greedy[1], r16);
+    if (lo) {
+      // EXPLORE law (DESIGN.md "Step semantics" 6), as dqn_act_kernel
+      const Word4 rw = pbn::draw(a.seed, ge, a.step + (uint64_t)ks, pbn::kStreamExplore, 0);
+      const int act = (uint64_t)rw.x < p->eps_u ? (int)__umulhi(rw.y, (uint32_t)d.A) : ((l32 >> 4) ? g1 : g0);
+#pragma unroll
+      for (int w = 0; w < W; ++w) m[w] = action_mask_word(act, N, w);
+      if (live) {
+#pragma unroll
+        for (int w = 0; w < W; ++w) a.flipmask[CK(ks * plane + (size_t)w * n + le, (size_t)n_steps * plane, 48)] = m[w];
+        if (p->actions) p->actions[CK(ks * n + le, n_steps * n, 49)] = act;
+      }
+    }
+  }
+
   // ---- 1. all Philox calls of the group, two half-wave work lists
   PBN_STAMP(1);
   Word4 out[IT];
@@ -1194,7 +1263,9 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) pbn_step_wave(StepArgs a)
       r_row = pbn::start_pick(xhi, xlo, as, a.att_single != 0, [&](uint32_t i) { return att_first[i]; }, xr);
     }
     u2 = xhi;
-    if (random_actions) {
+    if constexpr (POLICY) {
+      // (m is the policy's, above)
+    } else if (random_actions) {
       actions_from_draw<W>(c_act, N, a.n1_magic, m);
       if (live) {
 #pragma unroll
@@ -2737,10 +2808,13 @@ __global__ void __launch_bounds__(256) pbn_reset_kernel(const int32_t* __restric
 // 16 probability bits.  make(w, b) receives the pair as std::integral_constant values and
 // returns the host stub of its instance; nullptr for any other pair.  (for_state_words and
 // for_prob_bits are its halves, for a caller that chooses something between the two.)
+// (The policy rollout's instances take a second argument, PolicyFn: the dispatchers return what
+// make returns.)
 using StepFn = void (*)(StepArgs);
+using PolicyFn = void (*)(StepArgs, PolicyArgs);
 
 template <typename F>
-StepFn for_state_words(int W, F f) {
+auto for_state_words(int W, F f) -> decltype(f(std::integral_constant<int, 1>{})) {
   switch (W) {
     case 1: return f(std::integral_constant<int, 1>{});
     case 2: return f(std::integral_constant<int, 2>{});
@@ -2751,7 +2825,7 @@ StepFn for_state_words(int W, F f) {
 }
 
 template <typename F>
-StepFn for_prob_bits(int B, F f) {
+auto for_prob_bits(int B, F f) -> decltype(f(std::integral_constant<int, 4>{})) {
   switch (B) {
     case 4: return f(std::integral_constant<int, 4>{});
     case 8: return f(std::integral_constant<int, 8>{});
@@ -2762,7 +2836,8 @@ StepFn for_prob_bits(int B, F f) {
 }
 
 template <typename Make>
-StepFn step_kernel_for(int W, int B, Make make) {
+auto step_kernel_for(int W, int B, Make make)
+    -> decltype(make(std::integral_constant<int, 1>{}, std::integral_constant<int, 4>{})) {
   return for_state_words(W, [&](auto w) { return for_prob_bits(B, [&](auto b) { return make(w, b); }); });
 }
 

@@ -13,6 +13,8 @@ double-DQN / Huber / clip_grad_norm_ / Adam step.  Here one frame covers a whole
     pbn_per_sample / _update     prioritised replay (replay.py, csrc/pbn_per.hip)   (HIP)
     pbn_ddqn_learn               _learn_step on a flat parameter buffer, 4 launches (HIP, MFMA)
     pbn_ddqn_schedule            a captured frame's beta step and due target copy   (HIP)
+    pbn_rollout_dqn              n frames of the first two in one launch: the network runs inside
+                                 the multi-step step kernel (BatchedDDQN.rollout)   (HIP, MFMA)
 
 ``DQN`` keeps ddqn_per/network.py's module tree and parameter names, so the ``"params"`` entry of
 a reference ``ddqn_*.pt`` loads with ``load_state_dict``.  ``ddqn_update`` restates ``_get_loss`` +
@@ -293,6 +295,35 @@ class BatchedDDQN:
         """One frame for every env; returns (state', reward, flags) views as VectorPBNEnv.step_flipmask."""
         self.act_q(epsilon)
         return self.env.step_flipmask(use_current=True)
+
+    @torch.no_grad()
+    def rollout(self, n_steps: int, epsilon: Optional[float] = None, *, keep_obs: bool = False,
+                keep_final: bool = True, keep_updates: bool = False, out: Optional[dict] = None) -> dict:
+        """``n_steps`` frames of ``step()`` in one ``pbn_rollout_dqn`` launch: the wave that owns an
+        env runs the network on its state and target before every step, so the state never leaves
+        the chip.  Returns ``VectorPBNEnv.rollout``'s dict plus ``"actions"`` (int32 (n_steps,
+        n_alloc)); every entry equals what ``n_steps`` calls of ``act_q`` + ``step_flipmask`` give,
+        bit for bit.  The network is the agent's current image; ``env.step_index`` advances by
+        ``n_steps``.  Pass ``out`` (a previous result) to reuse its buffers."""
+        if not self.kernel:
+            raise ValueError("rollout runs the policy inside the step kernel, which takes a GPU env and a DQN with "
+                             "one hidden Linear, widths <= 64, N + 1 <= 128 (kernel=True)")
+        env = self.env
+        n_steps = int(n_steps)
+        if out is None or out["_n_steps"] != n_steps or out.get("actions") is None:
+            out = env.rollout_buffers(n_steps, keep_obs, keep_final, keep_updates, keep_actions=True)
+        eps = self.epsilon if epsilon is None else float(epsilon)
+        image = self.image()
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        with torch.cuda.device(env.device):
+            _lib.check(_lib.load().pbn_rollout_dqn(
+                env.net.handle, env.seed, env.step_index, env.env_offset, env.n_alloc, n_steps,
+                _lib.MODE_AUTORESET if env.autoreset else 0, env.state.data_ptr(), env.target.data_ptr(),
+                env.t.data_ptr(), self.h0, self.h1, image.data_ptr(), eps, out["flipmask"].data_ptr(),
+                out["actions"].data_ptr(), ptr(out["obs"]), ptr(out["final_state"]), out["reward"].data_ptr(),
+                out["flags"].data_ptr(), ptr(out.get("updates")), env._stream()), "pbn_rollout_dqn")
+        env.step_index += n_steps
+        return out
 
 
 class FusedDDQNUpdate(FusedUpdate):

@@ -53,14 +53,21 @@ def _spec_of(env) -> EnvSpec:
 
 def compute_ssd_hist(env, model: Optional[Callable] = None, resets: int = 300, iters: int = 100_000,
                      multiprocess: bool = False, *, burn_in: int = 0, seed: int = 0, chunk: int = 200,
-                     device=None, graph: bool = True) -> Tuple[np.ndarray, None]:
+                     device=None, graph: bool = True, fused: Optional[bool] = None) -> Tuple[np.ndarray, None]:
     """Returns (ssd, plot): ssd[s] = fraction of counted steps spent in state s (float64,
     2^N entries, state s = bit i for node i); plot is None (no plotting backend here).
 
-    ``model``: None (no interventions) or a policy mapping the (resets, N) uint8 state bits on
-    the GPU to (resets, k) actions in [0, N] (0 = no-op), called every step.
+    ``model``: None (no interventions); a ``DQN``, or a ``BatchedDDQN`` whose network is taken
+    (the reference's trained DDQN agent, train_ddqn.py:156), acting greedily (epsilon 0) on each
+    chain's state and the target its reset drew; or a policy mapping the (resets, N) uint8 state
+    bits on the GPU to (resets, k) actions in [0, N] (0 = no-op), called every step.
     ``multiprocess`` is accepted for signature compatibility; chains already run in parallel.
-    ``graph``: with a model, capture one policy step (state unpack, model, flip masks,
+    ``fused`` (a ``DQN`` only; default: whenever the step kernel takes the network, see
+    ``BatchedDDQN``): the chains run as ``BatchedDDQN.rollout`` launches of ``chunk`` steps, the
+    network evaluated inside the step kernel, exactly as the chains without a model do;
+    ``fused=False`` runs one ``act_q`` + ``pbn_step_dev`` + histogram per step.  Both give the same
+    histogram.
+    ``graph``: with a per-step model, capture one policy step (state unpack, model, flip masks,
     pbn_step_dev, histogram) in a hipGraph after a first eager step has validated the
     actions, and replay it; a model that cannot be captured (host syncs) raises, and
     ``graph=False`` runs every step eagerly.  Both give the same histogram.
@@ -77,28 +84,44 @@ def compute_ssd_hist(env, model: Optional[Callable] = None, resets: int = 300, i
     venv.reset()
     hist = torch.zeros(1 << N, dtype=torch.int32, device=dev)
     n = venv.n_alloc
+    from .ddqn import DQN, BatchedDDQN      # (ddqn.py imports this package's env modules)
+    agent = None
+    if isinstance(model, (DQN, BatchedDDQN)):
+        agent = BatchedDDQN(venv, model.q if isinstance(model, BatchedDDQN) else model, epsilon=0.0)
+    if fused is None:
+        fused = agent is not None and agent.kernel
+    if fused and agent is None:
+        raise ValueError("fused=True needs a DQN (or a BatchedDDQN): the step kernel evaluates no other model")
+
+    def run_chunks(roll) -> None:
+        """burn-in, then the counted steps, as launches of ``chunk`` steps: roll(k, keep_final, out)"""
+        left = burn_in
+        while left > 0:
+            k = min(chunk, left)
+            roll(k, False, None)
+            left -= k
+        left, buf = iters, None
+        while left > 0:
+            k = min(chunk, left)
+            buf = roll(k, True, buf if buf is not None and buf["_n_steps"] == k else None)
+            state_histogram(buf["final_state"].view(k, n), resets, N, hist)
+            left -= k
+
     with torch.cuda.device(dev):
         if model is None:
-            left = burn_in
-            buf = None
-            while left > 0:
-                k = min(chunk, left)
-                buf = venv.rollout(k, random_actions=False, keep_final=False)
-                left -= k
-            left, buf = iters, None
-            while left > 0:
-                k = min(chunk, left)
-                buf = venv.rollout(k, random_actions=False, keep_final=True,
-                                   out=buf if buf is not None and buf["_n_steps"] == k else None)
-                state_histogram(buf["final_state"].view(k, n), resets, N, hist)
-                left -= k
+            run_chunks(lambda k, keep, out: venv.rollout(k, random_actions=False, keep_final=keep, out=out))
+        elif fused:
+            run_chunks(lambda k, keep, out: agent.rollout(k, 0.0, keep_final=keep, out=out))
         else:
             step_t = torch.full((1,), venv.step_index, dtype=torch.int64, device=dev)
 
             def policy_step(count: bool, check: bool) -> None:
-                bits = unpack_states(venv.state[:, :resets], N)
-                fm = actions_to_flipmask(model(bits).to(dev), N, check=check)
-                venv.flipmask[:, :resets].copy_(fm)
+                if agent is not None:
+                    agent.act_q(0.0, step_t)
+                else:
+                    bits = unpack_states(venv.state[:, :resets], N)
+                    fm = actions_to_flipmask(model(bits).to(dev), N, check=check)
+                    venv.flipmask[:, :resets].copy_(fm)
                 venv.step_flipmask_dev(step_t)
                 step_t.add_(1)
                 if count:

@@ -225,14 +225,18 @@ class VectorPBNEnv:
                        "pbn_step_dev_store")
 
     def rollout_buffers(self, n_steps: int, keep_obs: bool = False, keep_final: bool = True,
-                        keep_updates: bool = False) -> dict:
+                        keep_updates: bool = False, *, keep_actions: bool = False) -> dict:
         """Output buffers of an ``n_steps`` rollout.  Uninitialised: the kernel writes every
         element of every buffer it is given (all ``n_alloc`` envs, all steps), and ``rollout``
         writes the flip masks itself when it does not draw them.  Allocate them before a
         hipGraph capture so that the graph holds the rollout launch alone.  ``keep_updates``:
-        the synchronous updates of every env-step (uint16; the settle length under the settle law)."""
+        the synchronous updates of every env-step (uint16; the settle length under the settle law).
+        ``keep_actions``: also ``actions`` (int32 (n_steps, n_alloc)), which a policy rollout
+        (``BatchedDDQN.rollout``) writes."""
         W, n, dev = self.words, self.n_alloc, self.device
-        return {"_n_steps": n_steps,
+        actions = {"actions": torch.empty(n_steps, n, dtype=torch.int32, device=dev)} if keep_actions else {}
+        return {**actions,
+                "_n_steps": n_steps,
                 "flipmask": torch.empty(n_steps, W, n, dtype=torch.int32, device=dev),
                 "reward": torch.empty(n_steps, n, dtype=torch.float32, device=dev),
                 "flags": torch.empty(n_steps, n, dtype=torch.uint8, device=dev),

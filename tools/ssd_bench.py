@@ -50,6 +50,72 @@ def gpu_chain_time(spec, resets, iters, chunk=200):
     return a.elapsed_time(b) / 1e3, total
 
 
+def _spread(xs):
+    return {"median": float(np.median(xs)), "min": float(min(xs)), "max": float(max(xs)), "runs": [float(x) for x in xs]}
+
+
+def policy_times(spec, resets, iters, policy_iters, blocks, net_arch=((50, 50),), weight_seed=0):
+    """compute_ssd_hist with a DQN policy, three ways, in alternating blocks of one call each at
+    ``policy_iters`` counted steps (wall time of the whole call / policy_iters = seconds per step):
+
+      fused      the network inside the step kernel (BatchedDDQN.rollout chunks)
+      per_step   fused=False: act_q + pbn_step_dev + histogram, one captured graph per step
+      closure    what a DQN policy cost before compute_ssd_hist took one: a closure calling the
+                 same module in PyTorch on unpack_states' bits (graph=True).  A closure cannot see
+                 the chains' targets, so it passes attractor 0's first state for every chain: its
+                 time is comparable, its histogram is not.
+
+    then one fused call at ``iters`` counted steps."""
+    from pbn_rl_amd.ddqn import DQN
+
+    torch.manual_seed(weight_seed)
+    N = spec.n
+    q = DQN(N, N + 1, list(net_arch)).cuda()
+    goal = torch.tensor(list(spec.attractors[0][0]), dtype=torch.float32, device="cuda").unsqueeze(0)
+
+    @torch.no_grad()
+    def closure(bits):
+        s = bits.to(torch.float32)
+        return q(s, goal.expand(s.shape[0], -1)).argmax(1, keepdim=True)
+
+    def timed(model, n_iters, **kw):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ssd, _ = compute_ssd_hist(spec, model, resets=resets, iters=n_iters, **kw)
+        dt = time.perf_counter() - t0
+        assert abs(float(ssd.sum()) - 1.0) < 1e-9
+        return dt, ssd
+
+    ways = {"fused": (q, {}), "per_step": (q, {"fused": False}), "closure": (closure, {})}
+    for model, kw in ways.values():       # warm-up: code objects, allocator, the graphs' first capture
+        timed(model, 200, **kw)
+    runs = {k: [] for k in ways}
+    calls = {k: [] for k in ways}
+    ssds = {}
+    short = 200
+    for _ in range(blocks):
+        for k, (model, kw) in ways.items():
+            base, _ = timed(model, short, **kw)
+            dt, ssds[k] = timed(model, policy_iters, **kw)
+            runs[k].append((dt - base) / (policy_iters - short))
+            calls[k].append(dt)
+    assert np.array_equal(ssds["fused"], ssds["per_step"])
+    whole_s, _ = timed(q, iters)
+    res = {k: _spread(v) for k, v in runs.items()}
+    return {"policy": f"DQN({N}, {N + 1}, {list(net_arch)}), torch.manual_seed({weight_seed}), greedy",
+            "policy_iters": policy_iters, "blocks": blocks,
+            "per_step_s": res,
+            "per_step_note": f"(call at policy_iters - call at {short} counted steps, back to back) / the difference "
+                             "in steps: the call's fixed cost (the 2^N-bin histogram's allocation, copy to the host "
+                             "and normalisation, the reset, graph capture) cancels",
+            "call_s": {k: _spread(v) for k, v in calls.items()},
+            "fused_whole_call_s": whole_s, "fused_whole_call_iters": iters,
+            "fused_vs_closure": res["closure"]["median"] / res["fused"]["median"],
+            "fused_vs_per_step": res["per_step"]["median"] / res["fused"]["median"],
+            "fused_below_closure_by_more_than_spread": bool(res["fused"]["max"] < res["closure"]["min"]),
+            "fused_equals_per_step_histogram": True}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--network", default="pbn28")
@@ -57,9 +123,16 @@ def main():
     ap.add_argument("--iters", type=int, default=100_000)
     ap.add_argument("--perturbation", type=float, default=0.01)
     ap.add_argument("--cpu-seconds", type=float, default=5.0)
+    ap.add_argument("--policy", choices=["none", "ddqn"], default="none",
+                    help="ddqn: also time compute_ssd_hist with a DQN policy (fused, per-step, PyTorch closure)")
+    ap.add_argument("--policy-iters", type=int, default=20_000, help="counted steps of each timed policy call")
+    ap.add_argument("--blocks", type=int, default=5, help="alternating blocks of the policy timings")
     args = ap.parse_args()
     spec = EnvSpec(load_network(args.network), load_attractors(args.network), perturbation=args.perturbation)
     steps = args.resets * args.iters
+    policy = None
+    if args.policy == "ddqn":
+        policy = policy_times(spec, args.resets, args.iters, args.policy_iters, args.blocks)
 
     gpu_chain_time(spec, args.resets, 1000)                      # warm-up (allocator, code objects)
     chain_s, counted = gpu_chain_time(spec, args.resets, args.iters)
@@ -87,11 +160,14 @@ def main():
         s, tt = r["final_state"], r["t"]
         k += 1
     py_rate = k / (time.perf_counter() - t0)
+    if policy is not None:
+        policy["fused_whole_call_vs_model_less"] = policy["fused_whole_call_s"] / total_s
     print(json.dumps({
         "what": f"compute_ssd_hist({args.network}, model=None, resets={args.resets}, iters={args.iters}), "
                 f"p={args.perturbation}, 2^{spec.n} 32-bit bins in HBM",
         "env_steps": steps, "gpu_chain_s": chain_s, "gpu_env_steps_per_s": steps / chain_s,
         "total_s": total_s,
+        **({"ddqn_policy": policy} if policy is not None else {}),
         "total_note": "includes the 2^N-bin device-to-host copy and float64 normalisation on the host",
         "cpu_c_oracle_env_steps_per_s": c_rate, "cpu_c_oracle_threads": threads,
         "cpu_c_oracle_est_s": steps / c_rate,
