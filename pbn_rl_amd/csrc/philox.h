@@ -96,6 +96,65 @@ __host__ __device__ __forceinline__ Word4 philox_rk(uint32_t c0, uint32_t c1, ui
   return Word4{c0, c1, c2, c3};
 }
 
+// The part of philox_rk's first three rounds that does not depend on counter word 1.  A loop that
+// calls with (c0, c2, c3) and the key fixed and only c1 (the step's low word) moving builds it once
+// in front of the loop (pbn_rollout_pipe's RNG waves).  With one round written as
+//   n0 = hi(M1 * c2) ^ c1 ^ k0,  n2 = hi(M0 * c0) ^ c3 ^ k1,  c1' = lo(M1 * c2),  c3' = lo(M0 * c0)
+// and (a, b, d) the counters after rounds 1, 2, 3:
+//   round 1: both products are fixed; a0 = A ^ c1, and a1, a2, a3 are fixed;
+//   round 2: M1 * a2 is fixed, so b0 and b1 are; b2 = hi(M0 * a0) ^ B, b3 = lo(M0 * a0);
+//   round 3: M0 * b0 is fixed, so d3 is; d0 = hi(M1 * b2) ^ D, d1 = lo(M1 * b2), d2 = b3 ^ E.
+// B and D depend on (c0, c3) and the key only: calls that differ in c2 alone share them.
+struct PhiloxPrefix {
+  uint32_t A, B, D, E, d3;
+};
+
+template <int R = kPhiloxRounds>
+__host__ __device__ __forceinline__ PhiloxPrefix philox_prefix(uint32_t c0, uint32_t c2, uint32_t c3,
+                                                                const uint32_t (&rk0)[R], const uint32_t (&rk1)[R]) {
+  static_assert(R >= 4, "the prefix covers rounds 1-3; the last round's XM belongs to the tail");
+  const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+  const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+  const uint32_t a1 = (uint32_t)p1, a3 = (uint32_t)p0;
+  const uint32_t a2 = xor3((uint32_t)(p0 >> 32), c3, rk1[0]);
+  const uint64_t q1 = (uint64_t)0xCD9E8D57u * a2;
+  const uint32_t b0 = xor3((uint32_t)(q1 >> 32), a1, rk0[1]);
+  const uint64_t s0 = (uint64_t)0xD2511F53u * b0;
+  PhiloxPrefix pre;
+  pre.A = (uint32_t)(p1 >> 32) ^ rk0[0];
+  pre.B = a3 ^ rk1[1];
+  pre.D = (uint32_t)q1 ^ rk0[2];
+  pre.E = (uint32_t)(s0 >> 32) ^ rk1[2];
+  pre.d3 = (uint32_t)s0;
+  return pre;
+}
+
+// philox_rk<R, XM>(c0, c1, c2, c3, rk0, rk1) from the prefix of (c0, c2, c3): one xor, one product
+// and one xor, one product and two xors, then rounds 4..R as they are
+template <int R = kPhiloxRounds, uint32_t XM = 0u>
+__host__ __device__ __forceinline__ Word4 philox_tail(const PhiloxPrefix& pre, uint32_t c1,
+                                                       const uint32_t (&rk0)[R], const uint32_t (&rk1)[R]) {
+  static_assert(R >= 4, "the prefix covers rounds 1-3; the last round's XM belongs to the tail");
+  const uint64_t p = (uint64_t)0xD2511F53u * (pre.A ^ c1);
+  const uint64_t q = (uint64_t)0xCD9E8D57u * ((uint32_t)(p >> 32) ^ pre.B);
+  uint32_t c0 = (uint32_t)(q >> 32) ^ pre.D;
+  c1 = (uint32_t)q;
+  uint32_t c2 = (uint32_t)p ^ pre.E;
+  uint32_t c3 = pre.d3;
+#pragma unroll
+  for (int r = 3; r < R; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = xor3((uint32_t)(p1 >> 32), c1, r == R - 1 ? (rk0[r] ^ XM) : rk0[r]);
+    const uint32_t n2 = xor3((uint32_t)(p0 >> 32), c3, r == R - 1 ? (rk1[r] ^ XM) : rk1[r]);
+    c1 = (uint32_t)p1;
+    c3 = (uint32_t)p0;
+    c0 = n0;
+    c2 = n2;
+  }
+  return Word4{c0, c1, c2, c3};
+}
+
 __host__ __device__ __forceinline__ Word4 draw(uint64_t seed, uint64_t id, uint64_t step,
                                                 uint32_t stream, uint32_t idx) {
   return philox((uint32_t)id, (uint32_t)step, (stream << 28) | (idx & 0x0FFFFFFFu),

@@ -1399,13 +1399,20 @@ __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
-// The running 64-bit step of an RNG wave's loop, held as its two words (wave-uniform: an SGPR
-// pair) and advanced by one: the low word wraps and the high word takes the carry, as
-// a.step + k does.  Written as the two instructions: the compiler would rebuild the sum from
-// a.step and the loop counter every step, and turn hi << 16 (counter word 3's step half: the
-// shift drops bits 48 and up, as the law's & 0xFFFF does) into a 64-bit shift and a mask.
-__device__ __forceinline__ void step_advance(uint32_t& lo, uint32_t& hi) {
-  asm("s_add_u32 %0, %0, 1\n\ts_addc_u32 %1, %1, 0" : "+s"(lo), "+s"(hi) : : "scc");
+// The running step of an RNG wave's fast loop: its low word (wave-uniform: an SGPR), advanced by
+// one.  The fast loops run only where every step of the launch has the same high word
+// (step_hi_fixed), so the word does not wrap and no carry leaves.  Written as the instruction: the
+// compiler would rebuild the sum from a.step and the loop counter every step.
+__device__ __forceinline__ void step_advance(uint32_t& lo) {
+  asm("s_add_u32 %0, %0, 1" : "+s"(lo) : : "scc");
+}
+
+// Do the steps first .. first + n_steps (the RNG waves compute one step ahead) share the high word
+// of the 64-bit step?  Then counter word 3 and with it the Philox prefix (philox.h) of every
+// per-step call are launch invariants.  A launch that crosses a multiple of 2^32 takes the general
+// role loops.
+__device__ __forceinline__ bool step_hi_fixed(uint64_t first, int n_steps) {
+  return (uint32_t)(first >> 32) == (uint32_t)((first + (uint64_t)n_steps) >> 32);
 }
 
 // ------------------------------- rollout kernel, three waves per pair of 32-env groups
@@ -1592,7 +1599,8 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
 
   // one loop per role: every wave passes the same n_steps + 1 block barriers, and each role's
   // loop-carried values (hoisted invariants) occupy registers only in that role's loop
-  if (role == 1 && (u_fl & 4u) && u_gx == 2 && u_na >= 2 && (u_fl & 16u) && (W > 1 || N <= 31)) {
+  const bool u_hi_fixed = step_hi_fixed(a.step, n_steps);   // wave-uniform: the fast RNG loops' Philox prefix holds
+  if (role == 1 && (u_fl & 4u) && u_gx == 2 && u_na >= 2 && (u_fl & 16u) && (W > 1 || N <= 31) && u_hi_fixed) {
     // env draws, common configuration (random actions, gap bucket table, two or more
     // single-state attractors): the same draws as the general loop below, branch-free apart from
     // the rare fourth-flip tail, so that the next step's ENV call
@@ -1603,18 +1611,21 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
     const uint32_t* att_words = L + a.att_off + u_na + 1;
     const uint2* lut = reinterpret_cast<const uint2*>(L + a.gap_lut_off);
     // the Philox key schedule, built once per wave (pinned: opaque SGPR values that are not
-    // rematerialised as adds of literals in the loop), and the running step of the ENV call being
-    // computed, one ahead of the step being drawn: advanced by one per step, its low word wraps
-    // and its high half carries as a.step + k does; the shift drops bits 48 and up
+    // rematerialised as adds of literals in the loop), and the low word of the running step of the
+    // ENV call being computed, one ahead of the step being drawn.  Counter word 3 (the env id's
+    // and the step's high halves; the shift drops bits 48 and up) is the same for every step of
+    // the launch (step_hi_fixed), so the part of the ENV call's first three rounds that does not
+    // depend on the step's low word is built once per lane (philox_prefix; pinned: opaque VGPR
+    // values whose products are not rematerialised in the loop)
     uint32_t rk0[pbn::kPhiloxRounds], rk1[pbn::kPhiloxRounds];
     pbn::philox_round_keys(k0, k1, rk0, rk1);
 #pragma unroll
     for (int r = 0; r < pbn::kPhiloxRounds; ++r) asm volatile("" : "+s"(rk0[r]), "+s"(rk1[r]));
-    const uint32_t ge_h16 = (uint32_t)((ge >> 32) & 0xFFFFu);
-    uint32_t step_lo = (uint32_t)a.step, step_hi = (uint32_t)(a.step >> 32);
-    auto env_call = [&]() {
-      return pbn::philox_rk((uint32_t)ge, step_lo, pbn::kStreamEnv << 28, ge_h16 | (step_hi << 16), rk0, rk1);
-    };
+    const uint32_t ge_hi = (uint32_t)((ge >> 32) & 0xFFFFu) | ((uint32_t)(a.step >> 32) << 16);
+    uint32_t step_lo = (uint32_t)a.step;
+    pbn::PhiloxPrefix pre = pbn::philox_prefix((uint32_t)ge, pbn::kStreamEnv << 28, ge_hi, rk0, rk1);
+    asm volatile("" : "+v"(pre.A), "+v"(pre.B), "+v"(pre.D), "+v"(pre.E), "+v"(pre.d3));
+    auto env_call = [&]() { return pbn::philox_tail(pre, step_lo, rk0, rk1); };
     StepRows<uint32_t> fm_rows = rows_open(a.flipmask, n, (size_t)n_steps * plane);
     // one step (k < n_steps; `odd` = k & 1, known at compile time: the slot costs no select):
     // this step's draws from E, the next step's ENV call into E_next
@@ -1642,7 +1653,7 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
         asm volatile("" ::: "memory");   // the LDS reads above are issued here
         __builtin_amdgcn_sched_barrier(0);
         PBN_PSTAMP_AT(k, 16);
-        step_advance(step_lo, step_hi);
+        step_advance(step_lo);
         E_next = env_call();   // (one unused call per launch)
         asm volatile("" : "+v"(E_next.x), "+v"(E_next.y), "+v"(E_next.z), "+v"(E_next.w));
         __builtin_amdgcn_sched_barrier(0);
@@ -1676,9 +1687,9 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
         for (int w = 0; w < W; ++w) rows_store(fm_rows, w, (size_t)w * n, le, valid, 8, m[w]);
         rows_advance(fm_rows, plane);
         if (p2 < N - 1) {   // rare: a fourth flip is possible
-          // this step's words: the running step is one ahead (a borrow where its low word wrapped)
-          const uint32_t step_lo_k = step_lo - 1u, step_hi_k = step_hi - (step_lo == 0u ? 1u : 0u);
-          const uint32_t ge_hi = ge_h16 | (step_hi_k << 16);
+          // this step's low word: the running step is one ahead (no borrow: step_hi_fixed).  Another
+          // counter word 2 than the prefix's, so the whole call
+          const uint32_t step_lo_k = step_lo - 1u;
           pbn::gap_tail<W>(
               0u, 3, p2, N, E,
               [&](int jj) { return pbn::philox_rk((uint32_t)ge, step_lo_k, pbn::gap_call_c2(0, jj), ge_hi, rk0, rk1); },
@@ -1786,7 +1797,7 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
       PBN_PSTAMP(k, 1);
       lds_barrier();
     }
-  } else if (role == 2 && W == 1 && u_mnf >= 2 && u_mnf <= kNodeRecs) {
+  } else if (role == 2 && W == 1 && u_mnf >= 2 && u_mnf <= kNodeRecs && u_hi_fixed) {
     // selection, single-word states with at most kNodeRecs functions per node: branch-free over
     // the lanes (lanes past N, single-function nodes and thresholds past a node's last compute
     // values the padded chain ignores), one loop per threshold count, and the next step's
@@ -1800,14 +1811,26 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
       pbn::philox_round_keys(k0, k1, rk0, rk1);
 #pragma unroll
       for (int r = 0; r < pbn::kPhiloxRounds; ++r) asm volatile("" : "+s"(rk0[r]), "+s"(rk1[r]));
-      const uint32_t G_h16 = (uint32_t)((G >> 32) & 0xFFFFu);
-      uint32_t step_lo = (uint32_t)a.step, step_hi = (uint32_t)(a.step >> 32);
+      // the Philox prefixes of the node's CPN calls, built once per lane (philox_prefix; pinned as
+      // in env_fast): the calls differ in counter word 2 alone, so B and D are one pair for all of
+      // them and A, E, d3 are per call
+      const uint32_t G_hi = (uint32_t)((G >> 32) & 0xFFFFu) | ((uint32_t)(a.step >> 32) << 16);
+      uint32_t step_lo = (uint32_t)a.step;
+      uint32_t pre_B = 0, pre_D = 0, pre_A[CPN], pre_E[CPN], pre_d3[CPN];
+#pragma unroll
+      for (int c = 0; c < CPN; ++c) {
+        const pbn::PhiloxPrefix p =
+            pbn::philox_prefix((uint32_t)G, (pbn::kStreamSel << 28) | (uint32_t)(4 * l32 + c), G_hi, rk0, rk1);
+        if (c == 0) { pre_B = p.B; pre_D = p.D; }
+        pre_A[c] = p.A; pre_E[c] = p.E; pre_d3[c] = p.d3;
+        asm volatile("" : "+v"(pre_A[c]), "+v"(pre_E[c]), "+v"(pre_d3[c]));
+      }
+      asm volatile("" : "+v"(pre_B), "+v"(pre_D));
       auto sel_calls = [&](uint32_t (&d)[16]) {
-        const uint32_t G_hi = G_h16 | (step_hi << 16);
 #pragma unroll
         for (int c = 0; c < CPN; ++c) {
-          const Word4 o = pbn::philox_rk((uint32_t)G, step_lo, (pbn::kStreamSel << 28) | (uint32_t)(4 * l32 + c),
-                                         G_hi, rk0, rk1);
+          const Word4 o = pbn::philox_tail(pbn::PhiloxPrefix{pre_A[c], pre_B, pre_D, pre_E[c], pre_d3[c]}, step_lo,
+                                           rk0, rk1);
           d[4 * c + 0] = o.x; d[4 * c + 1] = o.y; d[4 * c + 2] = o.z; d[4 * c + 3] = o.w;
         }
       };
@@ -1816,7 +1839,7 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
         PBN_ISA_LOOP("sel_fast", NQ);
         PBN_PSTAMP(k, 0);
         {
-          step_advance(step_lo, step_hi);
+          step_advance(step_lo);
           sel_calls(nxt);   // (one unused set per launch)
 #ifdef PBN_STAMPS
 #pragma unroll
