@@ -289,6 +289,34 @@ int pbn_state_histogram(const uint32_t* d_states, int64_t n_rows, int64_t n_cols
                         int32_t n_bits, uint32_t* d_hist, void* stream);
 
 /*
+ * Visited-state count in a device hash table keyed by the full state (additive export of ABI 11;
+ * pbn_rl_amd/csrc/state_table.h states the table, the hash and the probe): the sparse form of
+ * pbn_state_histogram for networks of any width, with 64-bit counts.
+ *
+ * Input: element (row t, word w, column c) of d_states at t * n_words * col_stride +
+ * w * col_stride + c, c < n_cols <= col_stride -- the [steps][W][n] obs / final_state output of
+ * the rollouts with col_stride = n; columns past n_cols are not counted.  The key is the row's
+ * n_words words, the top one masked to n_bits (32 (n_words - 1) + 1 .. 32 n_words).  Flattened
+ * row t * n_cols + c adds d_row_counts[t * n_cols + c] visits (0 skips the row), or one where
+ * d_row_counts is null; n_rows * n_cols < 2^32 - 1.
+ *
+ * Table: capacity a power of two >= 64; d_owner u64 [capacity] (0 = empty, else epoch << 32 |
+ * claiming row + 1), d_keys u32 [n_words][capacity], d_counts u64 [capacity], d_used / d_lost
+ * u64 [1] (slots claimed; rows that found no slot).  The caller zeroes all five once, passes an
+ * epoch >= 1 that is larger in every later launch on the same table, and keeps used + rows of the
+ * launch <= capacity / 2, so that a probe always meets an empty slot and d_lost stays 0.
+ * Rehashing or merging a table is the same call over that table's d_keys (n_rows 1, n_cols =
+ * col_stride = its capacity) with its d_counts as d_row_counts.
+ *
+ * Asynchronous on `stream`; allocates and synchronises nothing.  An empty input returns PBN_OK
+ * without a launch; argument errors return PBN_EINVAL before any device call.
+ */
+int pbn_table_insert(const uint32_t* d_states, int64_t n_rows, int64_t n_cols, int64_t col_stride,
+                     int32_t n_words, int32_t n_bits, const uint64_t* d_row_counts, int64_t capacity,
+                     uint64_t* d_owner, uint32_t* d_keys, uint64_t* d_counts, uint64_t* d_used,
+                     uint64_t* d_lost, uint32_t epoch, void* stream);
+
+/*
  * Agent edges of the batched BDQ frame loop (bdq_model/__init__.py:69-98,172-177;
  * SURVEY.md 8(d) config 5).  The Q-network forward itself runs in PyTorch between them.
  *

@@ -8,5 +8,7 @@ Public surface:
   env.PBNEnv / make                  scalar gym-style facade (drop-in under train_BDQ.py)
   evaluate.evaluate_control          source -> target control evaluation of a trained agent
   ddqn.DQN / DDQNLearner             the reference's DDQN / DDQN-PER agent over the batched envs
+  ssd.compute_ssd_hist               steady-state distribution (dense bins, or sparse=True: any width)
+  state_table.StateTable             visited-state counts in a device hash table
 """
 __version__ = "0.1.0"

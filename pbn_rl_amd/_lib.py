@@ -33,10 +33,10 @@ EXPORTS = ["pbn_net_create", "pbn_net_destroy", "pbn_net_words", "pbn_reset", "p
            "pbn_eval_track", "pbn_eval_reduce", "pbn_per_store", "pbn_per_sample", "pbn_per_update",
            "pbn_bdq_td_loss_per", "pbn_bdq_learn_per", "pbn_dqn_layout", "pbn_dqn_image_floats", "pbn_dqn_pack",
            "pbn_dqn_flipmask_from_state", "pbn_ddqn_learn_workspace", "pbn_ddqn_learn", "pbn_ddqn_schedule",
-           "pbn_rollout_dqn", "pbn_last_error",
+           "pbn_rollout_dqn", "pbn_table_insert", "pbn_last_error",
            "pbn_abi_version"]
 SOURCES = ["pbn_env.hip", "pbn_settle.hip", "pbn_agent.hip", "pbn_qnet.hip", "pbn_learn.hip", "pbn_eval.hip",
-           "pbn_per.hip", "pbn_ddqn.hip"]
+           "pbn_per.hip", "pbn_ddqn.hip", "pbn_table.hip"]
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -229,6 +229,9 @@ def load() -> ctypes.CDLL:
         L.pbn_rollout_dqn.argtypes = [vp, u64, u64, u64, i64, i32, u32, vp, vp, vp, i32, i32, vp, f32, vp, vp, vp, vp,
                                       vp, vp, vp, vp]
         L.pbn_rollout_dqn.restype = ctypes.c_int
+    if hasattr(L, "pbn_table_insert"):   # (additive export of ABI 11: the visited-state hash table)
+        L.pbn_table_insert.argtypes = [vp, i64, i64, i64, i32, i32, vp, i64, vp, vp, vp, vp, vp, u32, vp]
+        L.pbn_table_insert.restype = ctypes.c_int
     L.pbn_abi_version.argtypes = []
     L.pbn_abi_version.restype = ctypes.c_int
     _lib = L

@@ -173,13 +173,20 @@ def bottom_sccs(net: Network, candidates: np.ndarray, *, prob_bits: int = 16, ma
 
 
 def simulate_visits(net: Network, *, chains: int = 65536, burn_in: int = 1000, window: int = 64, seed: int = 0,
-                    prob_bits: int = 16, device=None, chunk: int = 250) -> np.ndarray:
+                    prob_bits: int = 16, device=None, chunk: int = 250, table: bool = False,
+                    window_chunk: int = 64) -> np.ndarray:
     """The distinct states ((S, N) 0/1 rows) that ``chains`` GPU chains of ``net`` (uniform
     random starts, no perturbation or interventions) visit in the ``window`` steps after
-    ``burn_in`` steps."""
+    ``burn_in`` steps.
+
+    ``table``: run the window as launches of ``window_chunk`` steps whose states go into a device
+    hash table (state_table.py) instead of materialising window x chains x W words for
+    ``torch.unique``: the window is then bounded by the distinct states, not by its length.  The
+    result is the same set in the same order."""
     import torch
 
     from .spec import EnvSpec
+    from .state_table import StateTable
     from .vector_env import VectorPBNEnv
 
     spec = EnvSpec(net, [], perturbation=0.0, prob_bits=prob_bits, horizon=0)
@@ -194,9 +201,24 @@ def simulate_visits(net: Network, *, chains: int = 65536, burn_in: int = 1000, w
                 buf = env.rollout(k, random_actions=False, keep_obs=False, keep_final=False,
                                   out=buf if buf is not None and buf["_n_steps"] == k else None)
                 left -= k
-            out = env.rollout(window, random_actions=False, keep_obs=True, keep_final=False)
-            words = out["obs"][:, :, :chains].permute(0, 2, 1).reshape(-1, env.words)
-            words = torch.unique(words, dim=0).cpu().numpy().view(np.uint32)
+            if table:
+                if window_chunk < 1:
+                    raise ValueError("window_chunk must be at least 1")
+                seen = StateTable(net.n, dev)
+                left, buf = window, None
+                while left > 0:
+                    k = min(window_chunk, left)
+                    buf = env.rollout(k, random_actions=False, keep_obs=True, keep_final=False,
+                                      out=buf if buf is not None and buf["_n_steps"] == k else None)
+                    seen.add(buf["obs"], chains)
+                    left -= k
+                words = seen.items()[0]
+                # torch.unique's row order: by word 0 first, words compared as int32
+                words = words[np.lexsort(tuple(words[:, w].view(np.int32) for w in reversed(range(env.words))))]
+            else:
+                out = env.rollout(window, random_actions=False, keep_obs=True, keep_final=False)
+                words = out["obs"][:, :, :chains].permute(0, 2, 1).reshape(-1, env.words)
+                words = torch.unique(words, dim=0).cpu().numpy().view(np.uint32)
     finally:
         env.close()
     shifts = np.arange(32, dtype=np.uint32)
@@ -205,10 +227,11 @@ def simulate_visits(net: Network, *, chains: int = 65536, burn_in: int = 1000, w
 
 def discover_attractors(net: Network, *, chains: int = 65536, burn_in: int = 1000, window: int = 64, seed: int = 0,
                         prob_bits: int = 16, device=None, chunk: int = 250, max_box: int = 1 << 14,
-                        max_states: int = 1 << 20) -> Attractors:
-    """Bottom SCCs of ``net``'s STG that ``chains`` GPU chains reach within ``burn_in`` steps."""
+                        max_states: int = 1 << 20, table: bool = False, window_chunk: int = 64) -> Attractors:
+    """Bottom SCCs of ``net``'s STG that ``chains`` GPU chains reach within ``burn_in`` steps
+    (``table`` / ``window_chunk``: see ``simulate_visits``)."""
     bits = simulate_visits(net, chains=chains, burn_in=burn_in, window=window, seed=seed, prob_bits=prob_bits,
-                           device=device, chunk=chunk)
+                           device=device, chunk=chunk, table=table, window_chunk=window_chunk)
     return bottom_sccs(net, bits, prob_bits=prob_bits, max_box=max_box, max_states=max_states)
 
 

@@ -13,21 +13,23 @@ PBN are run from resets and the visited states are counted.  gym_PBN is not avai
 * every state s' after step ``burn_in + 1 .. burn_in + iters`` of every chain is counted
   (``pbn_state_histogram`` on the rollout's ``final_state``), and the counts are normalised.
 
-Histogram bins are full states, so networks with at most 32 nodes (2^N bins in HBM: 1 GiB
-of 32-bit counters for Bittner-28).
+The dense histogram's bins are full states, so networks with at most 32 nodes (2^N bins in HBM:
+1 GiB of 32-bit counters for Bittner-28).  ``sparse=True`` counts the visited states in a device
+hash table instead (state_table.py): any network the env runs, 64-bit counts, no 2^N array.
 """
 from __future__ import annotations
 
-from typing import Callable, Optional, Tuple
+from typing import Callable, Optional, Tuple, Union
 
 import numpy as np
 import torch
 
 from . import _lib
 from .spec import EnvSpec
+from .state_table import SparseSSD, StateTable
 from .vector_env import VectorPBNEnv, actions_to_flipmask, unpack_states
 
-__all__ = ["compute_ssd_hist", "state_histogram"]
+__all__ = ["compute_ssd_hist", "state_histogram", "SparseSSD"]
 
 
 def state_histogram(states: torch.Tensor, n_cols: int, n_bits: int, hist: torch.Tensor) -> None:
@@ -53,7 +55,9 @@ def _spec_of(env) -> EnvSpec:
 
 def compute_ssd_hist(env, model: Optional[Callable] = None, resets: int = 300, iters: int = 100_000,
                      multiprocess: bool = False, *, burn_in: int = 0, seed: int = 0, chunk: int = 200,
-                     device=None, graph: bool = True, fused: Optional[bool] = None) -> Tuple[np.ndarray, None]:
+                     device=None, graph: bool = True, fused: Optional[bool] = None, sparse: bool = False,
+                     capacity: int = 1 << 16,
+                     stats: Optional[dict] = None) -> Tuple[Union[np.ndarray, SparseSSD], None]:
     """Returns (ssd, plot): ssd[s] = fraction of counted steps spent in state s (float64,
     2^N entries, state s = bit i for node i); plot is None (no plotting backend here).
 
@@ -71,19 +75,38 @@ def compute_ssd_hist(env, model: Optional[Callable] = None, resets: int = 300, i
     pbn_step_dev, histogram) in a hipGraph after a first eager step has validated the
     actions, and replay it; a model that cannot be captured (host syncs) raises, and
     ``graph=False`` runs every step eagerly.  Both give the same histogram.
+    ``sparse``: count the visited states in a ``StateTable`` of initially ``capacity`` slots
+    instead of 2^N bins, and return (``SparseSSD``, None): any N the env supports, no limit on
+    resets * iters.  The chains are the dense call's (same envs, seeds and step indices), so for
+    N <= 32 ``SparseSSD.to_dense()`` equals the dense result exactly.  With a per-step model the
+    captured step stages its ``final_state`` into a (chunk, W, n) buffer at a device-held row, and
+    the host inserts the staged rows every ``chunk`` steps (the insert's epoch is a launch
+    argument and growth reallocates the table, so it stays out of the graph).  ``stats`` (a dict)
+    receives the table's final ``capacity``, ``n_growths`` and ``n_states``.
     """
     spec = _spec_of(env)
     N = spec.n
-    if N > 32:
-        raise ValueError("the SSD histogram has 2^N bins: networks with at most 32 nodes")
-    if resets * iters >= 1 << 32:
+    if N > 32 and not sparse:
+        raise ValueError("the SSD histogram has 2^N bins: networks with at most 32 nodes "
+                         "(sparse=True counts the visited states of any network)")
+    if resets * iters >= 1 << 32 and not sparse:
         # the histogram's bins are 32-bit counters: a fixed-point attractor could take every count
-        raise ValueError(f"resets * iters = {resets * iters} counted steps overflow the 32-bit bins (< 2^32)")
+        raise ValueError(f"resets * iters = {resets * iters} counted steps overflow the 32-bit bins (< 2^32; "
+                         "sparse=True counts in 64 bits)")
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     venv = VectorPBNEnv(spec, resets, seed=seed, device=dev, autoreset=False, keep_final_state=True)
     venv.reset()
-    hist = torch.zeros(1 << N, dtype=torch.int32, device=dev)
     n = venv.n_alloc
+    if sparse:
+        table = StateTable(N, dev, capacity=capacity)
+
+        def count_rows(fs: torch.Tensor) -> None:     # fs: (k, W, n) final states of k steps
+            table.add(fs, resets)
+    else:
+        hist = torch.zeros(1 << N, dtype=torch.int32, device=dev)
+
+        def count_rows(fs: torch.Tensor) -> None:
+            state_histogram(fs.view(fs.shape[0], n), resets, N, hist)
     from .ddqn import DQN, BatchedDDQN      # (ddqn.py imports this package's env modules)
     agent = None
     if isinstance(model, (DQN, BatchedDDQN)):
@@ -104,7 +127,7 @@ def compute_ssd_hist(env, model: Optional[Callable] = None, resets: int = 300, i
         while left > 0:
             k = min(chunk, left)
             buf = roll(k, True, buf if buf is not None and buf["_n_steps"] == k else None)
-            state_histogram(buf["final_state"].view(k, n), resets, N, hist)
+            count_rows(buf["final_state"])
             left -= k
 
     with torch.cuda.device(dev):
@@ -114,6 +137,17 @@ def compute_ssd_hist(env, model: Optional[Callable] = None, resets: int = 300, i
             run_chunks(lambda k, keep, out: agent.rollout(k, 0.0, keep_final=keep, out=out))
         else:
             step_t = torch.full((1,), venv.step_index, dtype=torch.int64, device=dev)
+            if sparse:   # the counted steps' final states, staged on the device for the host's inserts
+                stage = torch.empty(max(1, min(chunk, iters)), venv.words, n, dtype=torch.int32, device=dev)
+                stage_row = torch.zeros(1, dtype=torch.int64, device=dev)
+            staged = 0
+
+            def flush_stage() -> None:
+                nonlocal staged
+                if staged:
+                    count_rows(stage[:staged])
+                    stage_row.zero_()
+                    staged = 0
 
             def policy_step(count: bool, check: bool) -> None:
                 if agent is not None:
@@ -124,8 +158,11 @@ def compute_ssd_hist(env, model: Optional[Callable] = None, resets: int = 300, i
                     venv.flipmask[:, :resets].copy_(fm)
                 venv.step_flipmask_dev(step_t)
                 step_t.add_(1)
-                if count:
-                    state_histogram(venv.final_state.view(1, n), resets, N, hist)
+                if count and sparse:
+                    stage.index_copy_(0, stage_row, venv.final_state.unsqueeze(0))
+                    stage_row.add_(1)
+                elif count:
+                    count_rows(venv.final_state.unsqueeze(0))
 
             venv.flipmask.zero_()      # padding envs (n_alloc > resets) are never intervened on
             total = burn_in + iters
@@ -144,6 +181,17 @@ def compute_ssd_hist(env, model: Optional[Callable] = None, resets: int = 300, i
                         graphs[count] = g
                     g.replay()
                 it += 1
+                if sparse and count:
+                    staged += 1
+                    if staged == stage.shape[0]:
+                        flush_stage()
+            flush_stage()
+        if sparse:
+            words, cnt = table.items()
+            if stats is not None:
+                stats.update(capacity=table.capacity, n_growths=table.n_growths, n_states=len(cnt))
+            venv.close()
+            return SparseSSD(words, cnt, N), None
         counts = hist.cpu().numpy().view(np.uint32)
     total = int(counts.sum(dtype=np.uint64))     # the bins are unsigned 32-bit counts
     venv.close()

@@ -1,6 +1,7 @@
 """Time compute_ssd_hist at the reference's evaluation settings.
 
     python tools/ssd_bench.py [--network pbn28] [--resets 300] [--iters 100000]
+    python tools/ssd_bench.py --sparse       # dense against sparse=True, and pbn70 (sparse only)
 
 The reference calls compute_ssd_hist(env, model, resets=300, iters=100_000) after every
 training run (train_pbn_28.py:257).  Prints one JSON line:
@@ -9,6 +10,9 @@ training run (train_pbn_28.py:257).  Prints one JSON line:
   cpu_*         the same env-steps priced at the CPU restatements' measured rates (bounded
                 samples: the C oracle on host threads over the same number of chains, and
                 the per-env pure-Python step), not run to completion
+--sparse times the dense call and compute_ssd_hist(sparse=True) (the visited-state hash table,
+state_table.py) in alternating blocks in one process, then one sparse call on pbn70, and writes
+profiles/ssd_sparse_pbn28.json (``sparse_times``).
 """
 import argparse
 import json
@@ -116,6 +120,104 @@ def policy_times(spec, resets, iters, policy_iters, blocks, net_arch=((50, 50),)
             "fused_equals_per_step_histogram": True}
 
 
+def gpu_sparse_chain_time(spec, resets, iters, capacity, chunk=200):
+    """gpu_chain_time with the table insert in place of the histogram (growth included)."""
+    from pbn_rl_amd.state_table import StateTable
+    venv = VectorPBNEnv(spec, resets, seed=0, autoreset=False, keep_final_state=True)
+    venv.reset()
+    table = StateTable(spec.n, venv.device, capacity=capacity)
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    left, buf = iters, None
+    while left > 0:
+        k = min(chunk, left)
+        buf = venv.rollout(k, random_actions=False, keep_final=True,
+                           out=buf if buf is not None and buf["_n_steps"] == k else None)
+        table.add(buf["final_state"], resets)
+        left -= k
+    b.record()
+    torch.cuda.synchronize()
+    total, lost = table.total, table.n_lost
+    venv.close()
+    return a.elapsed_time(b) / 1e3, total, lost
+
+
+def sparse_times(resets, iters, perturbation, blocks, out_path):
+    """The dense call against compute_ssd_hist(sparse=True) on pbn28 at the reference's settings, in
+    alternating blocks of one call each in this process: dense; sparse from the default capacity
+    (the table grows during the call); sparse pre-sized to the capacity the first sparse call ended
+    with (no growth).  Then the GPU time of the chunks alone (HIP events: rollout + histogram /
+    rollout + insert), and one sparse call on pbn70, which the dense path cannot run."""
+    spec = EnvSpec(load_network("pbn28"), load_attractors("pbn28"), perturbation=perturbation)
+    spec70 = EnvSpec(load_network("pbn70"), load_attractors("pbn70"), perturbation=perturbation)
+
+    def timed(sp, **kw):
+        stats = {}
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if kw.get("sparse"):
+            kw["stats"] = stats
+        ssd, _ = compute_ssd_hist(sp, None, resets=resets, iters=iters, **kw)
+        return time.perf_counter() - t0, ssd, stats
+
+    # warm-up: code objects, allocator (a short call of each kind), and the capacity to pre-size to
+    compute_ssd_hist(spec, None, resets=resets, iters=400)
+    compute_ssd_hist(spec, None, resets=resets, iters=400, sparse=True)
+    _, first, stats = timed(spec, sparse=True)
+    cap = stats["capacity"]
+    runs = {"dense": [], "sparse": [], "sparse_presized": []}
+    dense = ssd = None
+    for _ in range(blocks):
+        dt, dense, _ = timed(spec)
+        runs["dense"].append(dt)
+        dt, ssd, grown = timed(spec, sparse=True)
+        runs["sparse"].append(dt)
+        dt, pre, sized = timed(spec, sparse=True, capacity=cap)
+        runs["sparse_presized"].append(dt)
+        assert sized["n_growths"] == 0
+        assert np.array_equal(pre.counts, ssd.counts) and np.array_equal(pre.words, ssd.words)
+    assert np.array_equal(ssd.to_dense(), dense)          # the same counts over the same total
+    del dense
+    gpu_chain_time(spec, resets, 1000)
+    dense_chain_s, counted = gpu_chain_time(spec, resets, iters)
+    assert counted == resets * iters
+    gpu_sparse_chain_time(spec, resets, 1000, 1 << 16)
+    grow_chain_s, total, lost = gpu_sparse_chain_time(spec, resets, iters, 1 << 16)
+    assert total == resets * iters and lost == 0
+    sized_chain_s, total, lost = gpu_sparse_chain_time(spec, resets, iters, cap)
+    assert total == resets * iters and lost == 0
+    compute_ssd_hist(spec70, None, resets=resets, iters=400, sparse=True)
+    dt70, ssd70, stats70 = timed(spec70, sparse=True)
+    assert ssd70.total == resets * iters
+    chain70_s, _, lost70 = gpu_sparse_chain_time(spec70, resets, iters, 1 << 16)
+    assert lost70 == 0
+    res = {
+        "what": f"compute_ssd_hist(pbn28, model=None, resets={resets}, iters={iters}), p={perturbation}: dense (2^28 "
+                f"32-bit bins) against sparse=True (visited-state hash table), {blocks} alternating blocks in one "
+                "process; wall time of each whole call, seconds",
+        "env_steps": resets * iters, "blocks": blocks,
+        "call_s": {k: _spread(v) for k, v in runs.items()},
+        "sparse_vs_dense": float(np.median(runs["sparse"]) / np.median(runs["dense"])),
+        "sparse_presized_vs_dense": float(np.median(runs["sparse_presized"]) / np.median(runs["dense"])),
+        "gpu_chunks_s": {"dense": dense_chain_s, "sparse": grow_chain_s, "sparse_presized": sized_chain_s},
+        "gpu_chunks_note": "HIP events around the rollout + histogram / rollout + insert launches of one run (the "
+                           "sparse figure from the default capacity includes the table's growth and its "
+                           "synchronisations)",
+        "distinct_states": len(ssd), "final_capacity": grown["capacity"], "growths": grown["n_growths"],
+        "presized_capacity": cap, "default_capacity": 1 << 16,
+        "sparse_to_dense_equals_dense": True,
+        "pbn70": {"what": f"compute_ssd_hist(pbn70, model=None, resets={resets}, iters={iters}, sparse=True), one call",
+                  "call_s": dt70, "gpu_chunks_s": chain70_s, "distinct_states": len(ssd70),
+                  "final_capacity": stats70["capacity"], "growths": stats70["n_growths"]},
+        "host": {"cpu_count": os.cpu_count()}}
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--network", default="pbn28")
@@ -127,7 +229,15 @@ def main():
                     help="ddqn: also time compute_ssd_hist with a DQN policy (fused, per-step, PyTorch closure)")
     ap.add_argument("--policy-iters", type=int, default=20_000, help="counted steps of each timed policy call")
     ap.add_argument("--blocks", type=int, default=5, help="alternating blocks of the policy timings")
+    ap.add_argument("--sparse", action="store_true",
+                    help="time dense against sparse=True on pbn28 (and sparse on pbn70); writes --sparse-out")
+    ap.add_argument("--sparse-out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles",
+                                                         "ssd_sparse_pbn28.json"))
     args = ap.parse_args()
+    if args.sparse:
+        print(json.dumps(sparse_times(args.resets, args.iters, args.perturbation, args.blocks, args.sparse_out)),
+              flush=True)
+        return
     spec = EnvSpec(load_network(args.network), load_attractors(args.network), perturbation=args.perturbation)
     steps = args.resets * args.iters
     policy = None
