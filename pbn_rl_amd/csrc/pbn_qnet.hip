@@ -756,7 +756,20 @@ __global__ void __launch_bounds__(64 * kWaves) qnet_tail_kernel(QnetArgs a) {
         if (k0 + j < H) store_head(k0 + j, oc[j]);
       }
     }
-    if constexpr (FLIP) {
+    if constexpr (FLIP && Plan::kS9Heads == 0) {
+      // StagePlan<4>: stage S9 has no room for a head, so head 0 (the value head) arrives here,
+      // alone in the first head stage: it gives v and is never dueled, never enters the flip mask
+      // and never writes actions
+      static_assert(Plan::kHPS == 1 && kPend == 0, "the value head's stage holds it alone");
+      if (first) {
+        v = __shfl(oc[0][0][0], lane & 15);   // value head output 0: register 0 of lane group 0
+      } else {
+        int kk[1] = {k0};   // k0 >= 1 past the first head stage
+        act_heads(std::integral_constant<int, 1>{}, oc, kk);
+      }
+    } else if constexpr (FLIP) {
+      // act_heads takes branch heads only (kk >= 1): head 0 gave v in stage S9, and k0 >= kS9Heads
+      static_assert(Plan::kS9Heads >= 1, "head 0 must not reach act_heads");
       if (kPend > 0 && first) {
         f32x4 ob[kNB][T16];
         int kk[kNB];

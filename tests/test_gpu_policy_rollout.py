@@ -132,9 +132,12 @@ def test_fused_rollout_equals_act_then_step_under_the_settle_law(net, arch, sett
 @pytest.mark.parametrize("net,arch,settle", [("pbn7", [(8, 8)], 0), ("bb33", [(50, 50)], 0), ("pbn7", [(8, 8)], 9)],
                          ids=["pbn7", "bb33", "pbn7-settle9"])
 def test_fused_rollout_steps_are_the_oracles(net, arch, settle):
+    steps_are_the_oracles(make_spec(net, settle), arch)
+
+
+def steps_are_the_oracles(spec, arch):
     """oracle.step on the launch's emitted flip masks, from the same reset: the launch's
     per-step outputs at every step, and the state, target and t every launch leaves."""
-    spec = make_spec(net, settle)
     n = 96
     env = make_env(spec, n)
     agent = BatchedDDQN(env, make_dqn(spec.n, arch))
