@@ -96,13 +96,17 @@ inline size_t kernel_lds_bytes(const RouteNet& n, Kernel k) {
 // pbn_step (rollout = false) runs the pipelined settle kernel on whole groups under the settle
 // law, else a wave kernel; PBN_ROLL=lean forces the wave kernel, PBN_ROLL=pipe changes nothing.
 // pbn_rollout runs a pipelined kernel where the net has one that fits kLdsPipeBytes; PBN_ROLL
-// overrides the LDS limit in both directions.  Networks with gates always run a wave kernel.
+// overrides that limit in both directions, but not the device's: a pipelined kernel that needs
+// more than kLdsDeviceBytes cannot be launched at all (raise_lds_limits skips it), so a forced
+// pipe takes the wave kernel there.  The host decides; no launch asks for more LDS than a CU has.
+// Networks with gates always run a wave kernel.
 inline Route route_launch(const RouteNet& n, bool rollout, bool whole_groups) {
   const bool can_pipe = !n.n_gates && (!n.settle || n.has_pipe_settle);
   bool pipe;
   if (rollout) {
-    pipe = can_pipe && (n.settle ? n.lds_settle : n.lds_pipe) <= kLdsPipeBytes;
-    if (n.force_roll) pipe = can_pipe && n.force_roll == 3;
+    const size_t pipe_bytes = n.settle ? n.lds_settle : n.lds_pipe;
+    pipe = can_pipe && pipe_bytes <= kLdsPipeBytes;
+    if (n.force_roll) pipe = can_pipe && n.force_roll == 3 && pipe_bytes <= kLdsDeviceBytes;
   } else {
     pipe = n.settle && whole_groups && can_pipe && n.lds_settle <= kLdsPipeBytes && n.force_roll != 2;
   }

@@ -250,7 +250,7 @@ void pick_kernels(const pbn::NetImage& im, pbn_net* net) {
 int raise_lds_limits(const pbn_net& net) {
   for (int k = 0; k < kNumKernels; ++k) {
     const size_t bytes = kernel_lds_bytes(net.route, (Kernel)k);
-    if (!net.kernels[k] || bytes > kLdsDeviceBytes) continue;   // unusable for this net; never picked
+    if (!net.kernels[k] || bytes > kLdsDeviceBytes) continue;   // unusable for this net: route_launch never picks it
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(net.kernels[k]),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
       return fail(PBN_EDEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
@@ -584,7 +584,8 @@ static int rollout_impl(pbn_net* net, uint64_t seed, uint64_t step, uint64_t env
   a.updates = d_updates;
   // the pipelined kernels for every network they support (they beat the one-wave-per-group
   // rollout at every measured size: profiles/r01_sweep_pbn28_variants_v4.jsonl); networks
-  // with gates (lowered wide functions) run the wave kernel.  PBN_ROLL=lean|pipe forces one.
+  // with gates (lowered wide functions) run the wave kernel.  PBN_ROLL=lean|pipe forces one (pipe:
+  // up to the LDS of a CU, route_launch).
   const Route r = route_launch(net->route, true, true);
   int threads = r.threads;
   if (r.kernel == kPipe) {

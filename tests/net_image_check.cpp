@@ -168,6 +168,36 @@ void routing() {
       }
 }
 
+// a pipelined kernel that needs more LDS than a CU has is never launched, forced or not: the
+// wave kernel runs, with the wave kernel's LDS, and no route asks for more than kLdsDeviceBytes
+void routing_at_the_device_limit() {
+  const size_t at = kLdsDeviceBytes, over = kLdsDeviceBytes + 4;
+  const size_t sizes[3] = {64 * 1024 + 4, at, over};
+  const int forces[3] = {0, 2, 3};
+  for (int settle = 0; settle < 2; ++settle)
+    for (int force : forces)
+      for (size_t pipe_bytes : sizes)
+        for (size_t settle_bytes : sizes)
+          for (int whole = 0; whole < 2; ++whole) {
+            const RouteNet n{(bool)settle, 0, true, force, 150000, pipe_bytes, settle_bytes};
+            const Route s = route_launch(n, false, (bool)whole), r = route_launch(n, true, true);
+            const size_t own = settle ? settle_bytes : pipe_bytes;
+            EXPECT(s.lds_bytes <= kLdsDeviceBytes && r.lds_bytes <= kLdsDeviceBytes);
+            EXPECT(s.kernel == (settle ? kWaveSettle : kWave1) && s.lds_bytes == n.lds_wave);   // all above 64 KB
+            if (force == 3 && own <= at) {
+              EXPECT(r.kernel == (settle ? kPipeSettle : kPipe) && r.lds_bytes == own && r.threads == 192 &&
+                     r.groups_per_block == 2);
+            } else {
+              EXPECT(r.kernel == (settle ? kWaveSettleLean : kWaveLean) && r.lds_bytes == n.lds_wave &&
+                     r.threads == 256 && r.groups_per_block == 4);
+            }
+          }
+  // the case that showed it: 100 nodes, 254 attractors (lds_pipe 157,728, lds_settle 174,176 bytes)
+  const RouteNet one{false, 0, true, 3, 150048, 157728, 174176}, law{true, 0, true, 3, 150048, 157728, 174176};
+  EXPECT(route_launch(one, true, true).kernel == kPipe && route_launch(one, true, true).lds_bytes == 157728);
+  EXPECT(route_launch(law, true, true).kernel == kWaveSettleLean && route_launch(law, true, true).lds_bytes == 150048);
+}
+
 }  // namespace
 
 int main() {
@@ -175,6 +205,7 @@ int main() {
   gate_and_two_state_attractor();
   rejected_after_the_hash();
   routing();
+  routing_at_the_device_limit();
   if (g_failed) return printf("net_image_check: %d failed\n", g_failed), 1;
   printf("net_image_check: ok\n");
   return 0;

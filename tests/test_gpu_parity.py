@@ -365,15 +365,15 @@ def test_step_ragged_env_counts(name, settle):
 # fast env loops take only nets with two or more single-state attractors, the bucket table and
 # random actions; pbn_reset has no gaps, masks or outcome).
 #
-# caller            | n_attr 0 / 1 / >= 2                  | multi-state | gap_exact 0 / 1 / 2                    | given masks / random        | tail taken                   | autoreset off        | horizon 0
-# wave one-step     | no_attractors_autoreset / branches / step_matches_oracle | branches | branches / from_random_states_no_perturbation / step_matches_oracle | step_matches_oracle modes 0-3 | high_perturbation_multi_flip_path | step_matches_oracle mode 0, 2 | from_random_states_no_perturbation
-# wave lean rollout | rollout_high_perturbation_and_no_attractors / branches / rollout_matches_oracle | branches | branches / branches / rollout_matches_oracle | rollout_matches_oracle mode 1 / 3 | rollout_high_perturbation_and_no_attractors | branches | branches
-# wave settle       | branches / branches / settle_step_matches_oracle | branches | branches / settle_pipe_caps (p = 0, lean: branches) / settle_step_matches_oracle | settle_step_matches_oracle mode 0 / 3 | settle_unsettled_flag_and_high_perturbation | settle_step_matches_oracle mode 0 | branches
-# pipe general      | rollout_high_perturbation_and_no_attractors / branches / rollout_matches_oracle mode 1 | branches | branches / branches / rollout_matches_oracle mode 1 | rollout_matches_oracle mode 1 / branches | branches | branches | branches
-# pipe env_fast     | - / - / rollout_matches_oracle mode 3 | -           | - / - / rollout_matches_oracle mode 3   | - / rollout_matches_oracle  | rollout_high_perturbation_and_no_attractors, branches (fast_tail_*) | - (random actions with autoreset off: branches) | branches
-# settle general    | branches / branches / settle_rollout_matches_oracle mode 1 | branches | branches / settle_pipe_caps_and_odd_groups / settle_rollout mode 1 | settle_rollout mode 1 / branches | branches | branches | branches
-# settle env_fast   | - / - / settle_rollout_matches_oracle mode 3 | -    | - / - / settle_rollout mode 3           | - / settle_rollout mode 3   | settle_unsettled_flag... (W = 2), branches (fast_tail_*) | branches | branches
-# reset             | no_attractors_autoreset / branches / every test | branches | -                               | -                           | -                            | -                    | -
+# caller            | n_attr 0 / 1 / >= 2                  | multi-state | gap_exact 0 / 1 / 2                    | given masks / random        | tail taken                   | autoreset off        | horizon 0 | hash probes > 1 / gates at W >= 3 (test_gpu_table_limits.py)
+# wave one-step     | no_attractors_autoreset / branches / step_matches_oracle | branches | branches / from_random_states_no_perturbation / step_matches_oracle | step_matches_oracle modes 0-3 | high_perturbation_multi_flip_path | step_matches_oracle mode 0, 2 | from_random_states_no_perturbation | hash_given_masks_step, collapse_random_actions_step / gate_limit_step, gates_and_many_attractors
+# wave lean rollout | rollout_high_perturbation_and_no_attractors / branches / rollout_matches_oracle | branches | branches / branches / rollout_matches_oracle | rollout_matches_oracle mode 1 / 3 | rollout_high_perturbation_and_no_attractors | branches | branches | hash_given_masks_rollout lean, collapse_random_actions_rollout lean / gate_limit_rollout
+# wave settle       | branches / branches / settle_step_matches_oracle | branches | branches / settle_pipe_caps (p = 0, lean: branches) / settle_step_matches_oracle | settle_step_matches_oracle mode 0 / 3 | settle_unsettled_flag_and_high_perturbation | settle_step_matches_oracle mode 0 | branches | hash_given_masks_settle_step, ..._settle_rollout lean / gate_limit_settle
+# pipe general      | rollout_high_perturbation_and_no_attractors / branches / rollout_matches_oracle mode 1 | branches | branches / branches / rollout_matches_oracle mode 1 | rollout_matches_oracle mode 1 / branches | branches | branches | branches | hash_given_masks_rollout pipe / - (gates: the wave kernels)
+# pipe env_fast     | - / - / rollout_matches_oracle mode 3 | -           | - / - / rollout_matches_oracle mode 3   | - / rollout_matches_oracle  | rollout_high_perturbation_and_no_attractors, branches (fast_tail_*) | - (random actions with autoreset off: branches) | branches | collapse_random_actions_rollout pipe / -
+# settle general    | branches / branches / settle_rollout_matches_oracle mode 1 | branches | branches / settle_pipe_caps_and_odd_groups / settle_rollout mode 1 | settle_rollout mode 1 / branches | branches | branches | branches | hash_given_masks_settle_rollout pipe / -
+# settle env_fast   | - / - / settle_rollout_matches_oracle mode 3 | -    | - / - / settle_rollout mode 3           | - / settle_rollout mode 3   | settle_unsettled_flag... (W = 2), branches (fast_tail_*) | branches | branches | collapse_random_actions_rollout settle_pipe / -
+# reset             | no_attractors_autoreset / branches / every test | branches | -                               | -                           | -                            | -                    | - | - (no lookup, no gates)
 @pytest.mark.parametrize("case", LAW_BRANCHES)
 def test_law_branches_step(case):
     """pbn_step (the wave kernel's one-step variant) on the nets of law_branch_specs: given masks

@@ -1,7 +1,8 @@
 """The descriptor compiler (csrc/net_image.h) on the CPU: every section of the table image and
 every launch scalar against tests/golden/net_image.json, which was recorded from the
-pbn_net_create that preceded the split (a dump added just before its first device call), and
-the stand-alone check program (tests/net_image_check.cpp)."""
+pbn_net_create that preceded the split (a dump added just before its first device call; the cases
+at the descriptor's limits, added later, from the unchanged builder), and the stand-alone check
+program (tests/net_image_check.cpp)."""
 import ctypes
 import hashlib
 import json
@@ -15,6 +16,7 @@ from pbn_rl_amd.attractors import load_attractors, random_state_targets
 from pbn_rl_amd.network import load_network
 from pbn_rl_amd.spec import EnvSpec
 from tests.synthetic import random_network, random_spec
+from tests.table_limits import limit_spec
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "..", "pbn_rl_amd", "csrc")
@@ -44,6 +46,11 @@ def cases():
     out += [("pbn7_no_attractors", lambda: EnvSpec(load_network("pbn7"), None))]
     out += [(f"rand{n}", lambda n=n: random_spec(n, 100 + n, max_funcs=6)) for n in (5, 33, 70, 100)]
     out += [("wide12", wide)]
+    # the descriptor's limits: hashes of 2 and 4 probes in 2^12 slots (the largest images: 150 KB of
+    # LDS at four state words), and gates up to plane 255 at one, three and four state words
+    out += [(name, lambda name=name: limit_spec(name)) for name in (
+        "hold28_a254", "hold20_s1000", "hold100_a254", "collapse70", "gates32_limit", "gates70_limit",
+        "gates128_limit")]
     return out
 
 
@@ -74,7 +81,11 @@ def summarise(scalars: dict, vectors: dict) -> dict:
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    so = tmp_path_factory.mktemp("net_image") / "libnet_image.so"
+    return build_shim(tmp_path_factory.mktemp("net_image"))
+
+
+def build_shim(folder):
+    so = os.path.join(str(folder), "libnet_image.so")
     subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-shared", "-fPIC", "-I", CSRC, "-o", str(so),
                     os.path.join(HERE, "net_image_shim.cpp")], check=True)
     L = ctypes.CDLL(str(so))
@@ -90,10 +101,16 @@ def shim(tmp_path_factory):
 
 def compile_spec(L, spec):
     """(rc, error, summary or None) of compile_net on spec.desc."""
+    rc, err, scalars, vectors = compile_raw(L, spec)
+    return rc, err, (None if scalars is None else summarise(scalars, vectors))
+
+
+def compile_raw(L, spec):
+    """(rc, error, scalars, vectors) of compile_net on spec.desc; None twice where it refuses."""
     rc, err = ctypes.c_int(-1), ctypes.create_string_buffer(256)
     h = L.ni_compile(ctypes.addressof(spec.desc), ctypes.byref(rc), err, 256)
     if not h:
-        return rc.value, err.value.decode(), None
+        return rc.value, err.value.decode(), None, None
     try:
         scalars, vectors = {}, {}
         for name in SCALARS:
@@ -105,7 +122,7 @@ def compile_spec(L, spec):
             p = L.ni_vector(h, name.encode(), ctypes.byref(n))
             assert n.value >= 0, name
             vectors[name] = np.ctypeslib.as_array(p, shape=(n.value,)).copy() if n.value else np.zeros(0, np.uint32)
-        return rc.value, err.value.decode(), summarise(scalars, vectors)
+        return rc.value, err.value.decode(), scalars, vectors
     finally:
         L.ni_free(h)
 
@@ -142,6 +159,13 @@ def test_cases_reach_every_builder_path(golden):
     assert sc["pbn7_no_attractors"]["n_attr"] == 0 and sc["pbn7_no_attractors"]["hash_bits"] == 0
     assert sc["wide12"]["n_gates"] > 0 and sc["wide12"]["n_glayers"] >= 2
     assert sc["pbn28_settle64"]["settle_max"] == 64
+    assert {s["hash_probes"] for s in sc.values()} == {0, 1, 2, 4}      # 0: no attractors
+    assert sc["hold28_a254"]["hash_probes"] == 2 and sc["hold20_s1000"]["hash_probes"] == 4
+    at_limit = [s for s in sc.values() if 32 * s["W"] + s["n_gates"] == 256]
+    assert {s["W"] for s in at_limit} >= {1, 3, 4}                       # plane 255 is a gate's output
+    assert all(s["wave_words"] == 256 and s["n_glayers"] == 4 for s in at_limit)
+    assert {s["W"] for s in sc.values() if s["n_gates"]} == {1, 2, 3, 4}
+    assert sc["hold100_a254"]["lds_settle"] > 160 * 1024 >= sc["hold100_a254"]["lds_pipe"] > 150 * 1024
 
 
 def test_compile_reports_the_reason(shim):
