@@ -84,13 +84,11 @@ class PerOracle:
         self.rebuild()
         return leaves
 
-    def p_total(self) -> float:
-        """sum(0, size - 1) of memory.py:123: leaves [0, size - 2] (reduce's end -= 1), in the
-        association of _reduce (data_structures.py:33-60): the left-sibling totals collected top
-        down, added as t_1 + (t_2 + (... + t_m))."""
+    def prefix_terms(self) -> list:
+        """The subtree totals whose sum is p_total, top down (t_1 .. t_m; [] below two rows)."""
         rem, w, node, t = self.size - 1, self.T, 1, []
         if rem < 1:
-            return 0.0
+            return t
         while True:
             if rem == w:
                 t.append(float(self.sum[node]))
@@ -102,6 +100,15 @@ class PerOracle:
                 t.append(float(self.sum[2 * node]))
                 node = 2 * node + 1
                 rem -= w
+        return t
+
+    def p_total(self) -> float:
+        """sum(0, size - 1) of memory.py:123: leaves [0, size - 2] (reduce's end -= 1), in the
+        association of _reduce (data_structures.py:33-60): the left-sibling totals collected top
+        down, added as t_1 + (t_2 + (... + t_m))."""
+        t = self.prefix_terms()
+        if not t:
+            return 0.0
         p = t[-1]
         for x in reversed(t[:-1]):
             p = x + p

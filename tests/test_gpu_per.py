@@ -59,12 +59,13 @@ def dev_update(rp, o, idx, prio):
     return o.update(idx, prio)
 
 
-def dev_sample(rp, o, B):
+def dev_sample(rp, o, B, size_t=None):
     """One device sample against the oracle (whose trees equal the device's bit for bit after
-    check_trees): rows exactly, weights within 1 fp32 ulp, beta and the counter advanced."""
+    check_trees): rows exactly, weights within 1 fp32 ulp, beta and the counter advanced.
+    ``size_t``: the fill level as a one-element device tensor, as a captured frame passes it."""
     beta, ctr = float(rp.beta_t), int(rp.counter_t)
     assert beta == rp.beta
-    idx, w = rp.sample(B)
+    idx, w = rp.sample(B, size_t)
     torch.cuda.synchronize()
     want_idx, want_w = o.sample(B, beta, replay_uniforms(SEED, ctr, B))
     assert np.array_equal(idx.cpu().numpy(), want_idx)
