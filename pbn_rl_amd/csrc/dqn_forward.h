@@ -1,6 +1,6 @@
 // dqn_forward.h -- the forward of ddqn_per/network.py's DQN (one hidden Linear) for 16 rows on one
 // wave, shared by the kernels of pbn_ddqn.hip (acting, the update's three forwards) and the policy
-// rollout of step_kernels.h (pbn_step_wave with a PolicyArgs): one function, so the policy
+// rollout of step_wave.h (pbn_step_wave with a PolicyArgs): one function, so the policy
 // rollout's actions are dqn_act's bit for bit.  Also the shapes and layouts (Dims) of the flat parameter buffer and of
 // the network image that forward16 reads (pbn_dqn_pack writes it).
 #pragma once
@@ -10,9 +10,9 @@
 #include <math.h>
 #include <stdint.h>
 
-namespace {
+#include "wave_util.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+namespace {
 
 constexpr int kMaxHT = 4;       // hidden widths <= 64: at most four 16-wide tiles
 constexpr int kMaxA = 128;      // N + 1 <= 128
@@ -83,10 +83,6 @@ inline void make_dims(int N, int W, int n_attr, int h0, int h1, Dims* d) {
 // epsilon = 1 always explores and 0 never does
 __host__ __device__ inline uint64_t explore_threshold(float epsilon) {
   return (uint64_t)floor((double)epsilon * 4294967296.0);
-}
-
-__device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
 // ---- the forward of 16 rows on one wave --------------------------------------------------------

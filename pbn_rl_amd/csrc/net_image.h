@@ -2,7 +2,7 @@
 // into LDS, the record and threshold arrays they read from global memory, and the scalars of
 // their launch arguments.  Plain C++17, free of HIP (tests/test_net_image.py runs it on the CPU);
 // pbn_net_create uploads the result.  Every step below appends its section to NetImage::tab and
-// records the section's offset; the kernels' view of the sections is StepArgs (step_kernels.h).
+// records the section's offset; the kernels' view of the sections is StepArgs (step_args.h).
 #pragma once
 #include <math.h>
 #include <stdint.h>

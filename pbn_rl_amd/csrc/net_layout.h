@@ -1,7 +1,9 @@
 // net_layout.h -- what the host-side descriptor compiler (net_image.h), the launcher
-// (pbn_env.hip) and the kernels (step_kernels.h) must agree on: table strides, the LDS carving
-// of the three step kernels, the LDS limits and the choice of kernel for a launch.  Plain
-// C++17, free of HIP.
+// (pbn_env.hip) and the kernels (step_wave.h, rollout_pipe.h, rollout_settle.h) must agree on:
+// table strides, the LDS carving of the three step kernels, the LDS limits and the choice of
+// kernel for a launch.  Each carving is stated once, as offsets: the host's LDS request is the
+// last offset, the kernels take their pointers from the same functions, and carving_ok (at the
+// end of the carving) asserts order, alignment and totals.  Plain C++17, free of HIP.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -31,9 +33,17 @@ PBN_HD constexpr int hash_stride(int W) { return W == 1 ? 2 : (W <= 3 ? 4 : 8); 
 // cycles per mask)
 PBN_HD constexpr int sel_mask_stride(int B) { return 4 * (((3 * B + 3) / 4) | 1); }
 
-// pbn_rollout_settle's ring of output rows (step_kernels.h "output rows in LDS")
+// pbn_rollout_settle's ring of output rows (rollout_settle.h "output rows in LDS"): R rows of the
+// block's 64 envs, a row's fields at these word offsets: final state [W][64] | observation
+// [W][64] | flip mask [W][64] | reward [64] | flags [64 bytes] | update counts [64 u16]
 PBN_HD constexpr int settle_stage_rows(int W) { return W == 1 ? 16 : (W == 2 ? 8 : 4); }
-PBN_HD constexpr int settle_row_words(int W) { return 3 * 64 * W + 64 + 16 + 32; }
+PBN_HD constexpr int settle_row_final(int) { return 0; }
+PBN_HD constexpr int settle_row_obs(int W) { return settle_row_final(W) + 64 * W; }
+PBN_HD constexpr int settle_row_flip(int W) { return settle_row_obs(W) + 64 * W; }
+PBN_HD constexpr int settle_row_reward(int W) { return settle_row_flip(W) + 64 * W; }
+PBN_HD constexpr int settle_row_flags(int W) { return settle_row_reward(W) + 64; }
+PBN_HD constexpr int settle_row_updates(int W) { return settle_row_flags(W) + 64 / 4; }
+PBN_HD constexpr int settle_row_words(int W) { return settle_row_updates(W) + 64 / 2; }
 constexpr int kStageOutWords = 12;   // StageOut: six output pointers
 
 // ---- LDS carving, in words; every kernel starts with the table image [tab_words] ----
@@ -45,30 +55,81 @@ constexpr size_t wave_lds_words(int tab_words, int wave_words) {
 }
 
 // the pipelined kernels: image | S planes of the block's two groups [64W] | 2 slots (by
-// iteration parity).  pbn_rollout_pipe's slot: flip mask, perturbation mask, reset state [3W][64]
-// | reset target [64] | selection planes [lq][64W]
+// iteration parity).  A slot is env-major, [64] words per field and state word, and its fields are
+// the same in both kernels: flip mask [W][64] | perturbation mask [W][64] | reset state [W][64] |
+// info [64] (pbn_rollout_pipe: reset target, action count, perturbed; pbn_rollout_settle: reset
+// target, action count) | selection planes [lq][64W]
 PBN_HD constexpr int pipe_planes_words(int W) { return 2 * 32 * W; }
-constexpr int pipe_slot_words(int W, int lq) { return (3 * W + 1) * 64 + lq * 64 * W; }
+PBN_HD constexpr int pipe_slot_flip(int) { return 0; }
+PBN_HD constexpr int pipe_slot_pert(int W) { return pipe_slot_flip(W) + 64 * W; }
+PBN_HD constexpr int pipe_slot_reset(int W) { return pipe_slot_pert(W) + 64 * W; }
+PBN_HD constexpr int pipe_slot_info(int W) { return pipe_slot_reset(W) + 64 * W; }
+PBN_HD constexpr int pipe_slot_sel(int W) { return pipe_slot_info(W) + 64; }
+PBN_HD constexpr int pipe_slot_words(int W, int lq) { return pipe_slot_sel(W) + lq * 64 * W; }
+PBN_HD constexpr int settle_slot_words(int W, int lq) { return pipe_slot_words(W, lq); }   // (the same slot)
 constexpr size_t pipe_lds_words(int tab_words, int W, int lq) {
   return (size_t)tab_words + (size_t)pipe_planes_words(W) + 2 * (size_t)pipe_slot_words(W, lq);
 }
 
-// pbn_rollout_settle's slot: flip mask, perturbation mask, reset state [3W][64] | reset target and
-// action count [64] | selection planes [lq][64W]; after the slots: ctl [2][64] uint4 | the packed
-// thresholds [lq][W][16] (rounded to 16 bytes) | the output rows | the stored-row counter by
-// parity [2] | the rows' output pointers (StageOut), the two padded to 16 bytes
-constexpr int settle_slot_words(int W, int lq) { return 192 * W + 64 + lq * 64 * W; }
+// pbn_rollout_settle, after the slots (word offsets from their end): ctl [2][64] uint4 | the
+// packed thresholds [lq][W][16] (rounded to 16 bytes) | the output rows | the stored-row counter
+// by parity [2] | the rows' output pointers (StageOut, uint64_t) | end, the two padded to 16 bytes
 constexpr int kSettleCtlVecs = 2 * 64;   // uint4
 PBN_HD constexpr int settle_thr_words(int W, int lq) { return (lq * W * 16 + 3) & ~3; }
 PBN_HD constexpr int settle_rows_words(int W) { return settle_stage_rows(W) * settle_row_words(W); }
 constexpr int kSettleRowCounterWords = 2;
-constexpr int settle_tail_words() { return (kSettleRowCounterWords + kStageOutWords + 3) & ~3; }
+struct SettleTail {   // (functions: a kernel pays for the lq arithmetic only where it asks for it)
+  int W, lq;
+  PBN_HD constexpr int ctl() const { return 0; }
+  PBN_HD constexpr int thr() const { return ctl() + 4 * kSettleCtlVecs; }
+  PBN_HD constexpr int rows() const { return thr() + settle_thr_words(W, lq); }
+  PBN_HD constexpr int counter() const { return rows() + settle_rows_words(W); }
+  PBN_HD constexpr int out() const { return counter() + kSettleRowCounterWords; }
+  PBN_HD constexpr int end() const { return (out() + kStageOutWords + 3) & ~3; }
+};
 constexpr size_t settle_lds_words(int tab_words, int W, int lq) {
   return (size_t)tab_words + (size_t)pipe_planes_words(W) + 2 * (size_t)settle_slot_words(W, lq) +
-         4 * (size_t)kSettleCtlVecs + (size_t)settle_thr_words(W, lq) + (size_t)settle_rows_words(W) +
-         (size_t)settle_tail_words();
+         (size_t)SettleTail{W, lq}.end();
 }
-static_assert(settle_tail_words() == 16, "row counter [2] | StageOut [12] | padding [2]");
+
+// The carvings above, checked for W state words and lq selection masks against each region's
+// width, written out once more below: the regions lie in order and do not overlap, what is read as
+// uint4 (ctl, the packed thresholds, a slot's rows through ds_read_b128; the table image is a
+// multiple of 16 bytes) or as uint64_t (StageOut) is aligned, and the LDS a launch asks for ends
+// where the last region ends.  (It catches an offset that no longer leaves room for its
+// neighbour, not a width changed here and above alike.)
+struct LdsRegion {
+  int at, words;
+};
+template <int N>
+constexpr bool lds_in_order(const LdsRegion (&r)[N], int end) {
+  for (int i = 0; i < N; ++i)
+    if (r[i].at < 0 || r[i].words < 0 || r[i].at + r[i].words > (i + 1 < N ? r[i + 1].at : end)) return false;
+  return r[0].at == 0;
+}
+constexpr bool carving_ok(int W, int lq) {
+  const LdsRegion slot[] = {{pipe_slot_flip(W), 64 * W}, {pipe_slot_pert(W), 64 * W}, {pipe_slot_reset(W), 64 * W},
+                            {pipe_slot_info(W), 64}, {pipe_slot_sel(W), lq * 64 * W}};
+  const LdsRegion row[] = {{settle_row_final(W), 64 * W}, {settle_row_obs(W), 64 * W}, {settle_row_flip(W), 64 * W},
+                        {settle_row_reward(W), 64}, {settle_row_flags(W), 64 / 4}, {settle_row_updates(W), 64 / 2}};
+  const SettleTail t = {W, lq};
+  const LdsRegion tail[] = {{t.ctl(), 4 * kSettleCtlVecs}, {t.thr(), lq * W * 16}, {t.rows(), settle_rows_words(W)},
+                         {t.counter(), kSettleRowCounterWords}, {t.out(), kStageOutWords}};
+  const int front = pipe_planes_words(W) + 2 * pipe_slot_words(W, lq);   // after the image, before the tail
+  return lds_in_order(slot, pipe_slot_words(W, lq)) && lds_in_order(slot, settle_slot_words(W, lq)) &&
+         lds_in_order(row, settle_row_words(W)) && lds_in_order(tail, t.end()) &&
+         pipe_slot_words(W, lq) % 4 == 0 && settle_row_words(W) % 4 == 0 && front % 4 == 0 && t.ctl() % 4 == 0 &&
+         t.thr() % 4 == 0 && t.rows() % 4 == 0 && (front + t.out()) % 2 == 0 && t.end() % 4 == 0 &&
+         pipe_lds_words(0, W, lq) == (size_t)front && settle_lds_words(0, W, lq) == (size_t)(front + t.end());
+}
+constexpr bool carvings_ok() {
+  for (int W = 1; W <= 4; ++W)
+    for (int lq = 1; lq <= 3; ++lq)
+      if (!carving_ok(W, lq)) return false;
+  return true;
+}
+static_assert(carvings_ok(), "the pipelined kernels' LDS carvings, W = 1..4, lq = 1..3");
+static_assert(SettleTail{1, 1}.end() - SettleTail{1, 1}.counter() == 16, "row counter [2] | StageOut [12] | padding [2]");
 
 // ---- which kernel a launch runs ----
 

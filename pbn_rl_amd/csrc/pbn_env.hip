@@ -555,7 +555,7 @@ static int rollout_impl(pbn_net* net, uint64_t seed, uint64_t step, uint64_t env
   int rc = check_common(net, env_offset, n_envs);
   if (rc) return rc;
   if (n_steps < 0) return fail(PBN_EINVAL, "n_steps < 0");
-  // a lane's byte offset into one output row is 32 bits wide (step_kernels.h LANE_AT, StepRows)
+  // a lane's byte offset into one output row is 32 bits wide (step_debug.h LANE_AT, StepRows)
   if (n_envs >= ((int64_t)1 << 30)) return fail(PBN_EINVAL, "n_envs must be below 2^30");
   bool copy_after = cp_bytes > 0;   // cleared when the copy rides along the launch
   struct After {   // the standalone copy, if it is still owed when the launch has been issued

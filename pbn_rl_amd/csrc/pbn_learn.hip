@@ -44,10 +44,9 @@
 #include "../../include/pbn_env.h"
 #include "net_view.h"
 #include "replay_draw.h"
+#include "wave_util.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kRows = 16;              // transitions per tile: the MFMA's 16 columns
 constexpr int kWaves = 8;              // waves per forward / backward block
@@ -172,20 +171,7 @@ constexpr int kLStampRow = 32;
 #define PBN_LSTAMP(k, i) do {} while (0)
 #endif
 
-__device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
 __device__ __forceinline__ float leaky(float x, float slope) { return x > 0.f ? x : x * slope; }
-
-// A block barrier that orders LDS only: the waves of learn_fwd / learn_bwd exchange nothing
-// through global memory, so a barrier need not wait for their global stores (on CDNA they count
-// in vmcnt with the loads) or for the weight fragments requested ahead.
-__device__ __forceinline__ void lds_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
 
 __device__ __forceinline__ int64_t row_index(const LearnArgs& a, int b) {
   const int64_t j = a.idx[b];

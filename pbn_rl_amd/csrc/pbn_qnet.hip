@@ -30,10 +30,10 @@
 #include "../../include/pbn_env.h"
 #include "net_view.h"
 #include "philox.h"
+#include "wave_util.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kD0 = 256, kD1 = 128, kD2 = 64, kD3 = 32, kDH = 64;   // BranchingQNetwork widths
@@ -89,10 +89,6 @@ constexpr int kQStampRow = 64;
 constexpr int kPitch = 36;                   // weight row pitch in LDS (floats): conflict-free float4 reads
 constexpr int kBufFloats = 5 * 64 * kPitch;  // one stage buffer: 320 rows (the largest stage, below)
 constexpr int kMaxPieces = 5;
-
-__device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 // acc = bias of the output features 16 m + 4 g + i (0 past n_out; b in LDS)
 __device__ __forceinline__ f32x4 bias_tile(const float* __restrict__ b, int m, int g, int n_out) {

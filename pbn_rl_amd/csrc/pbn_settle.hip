@@ -3,7 +3,9 @@
 // pipelined settle rollout pbn_rollout_settle, and the policy rollout's settle instance
 // (pbn_step_wave<W, B, 4, PolicyArgs>), compiled beside pbn_env.hip so that the kernel
 // instances build in parallel.
-#include "step_kernels.h"
+#include "rollout_settle.h"
+#include "step_small.h"
+#include "step_wave.h"
 
 namespace {
 

@@ -1,4 +1,4 @@
-"""The DDQN kernels (csrc/pbn_ddqn.hip, dqn_forward.h) and the policy rollout (step_kernels.h) at
+"""The DDQN kernels (csrc/pbn_ddqn.hip, dqn_forward.h) and the policy rollout (step_wave.h) at
 the action-tile and state-word edges of tests/edge_shapes.py, with hidden widths that differ
 (H0T != H1T), fill a 16-tile exactly and sit one past it: [(1, 1)], [(16, 17)], [(17, 64)] and
 [(64, 16)], each at W = 1 and at W = 4.

@@ -1,5 +1,5 @@
 """pbn_rollout's pipelined kernel with the Philox prefix hoisted out of its two fast RNG loops
-(csrc/philox.h philox_prefix / philox_tail, csrc/step_kernels.h env_fast / sel_fast) == the CPU
+(csrc/philox.h philox_prefix / philox_tail, csrc/rollout_pipe.h env_fast / sel_fast) == the CPU
 oracle, bit for bit.
 
 The fast loops build, per lane and in front of the step loop, the part of every per-step call's

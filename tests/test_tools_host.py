@@ -63,3 +63,41 @@ def test_handoff_summary_cuts_reps_at_gaps(tmp_path):
     assert d["reps"] == 2
     assert len(d["median_rep"]["items"]) == 3 and abs(d["median_rep"]["span_us"] - 220.0) < 1e-6
     assert len(d["median_bare_rep"]["items"]) == 2 and abs(d["median_bare_rep"]["span_us"] - 161.0) < 1e-6
+
+
+def _listing(order, cuid, body_b="v_add_u32_e32 v0, v1, v2"):
+    """A device listing in the compiler's shape: two kernels in the given order (the function index
+    in local labels follows the order), their descriptors, and the code object's metadata."""
+    body = {"kern_a": "v_mov_b32_e32 v0, 0", "kern_b": body_b}
+    out = ['\t.amdgcn_target "amdgcn-amd-amdhsa--gfx950"']
+    for i, k in enumerate(order):
+        out += ["\t.text", "\t.globl\t%s" % k, "\t.p2align\t8", "\t.type\t%s,@function" % k, "%s:" % k,
+                "\t" + body[k], "\ts_cbranch_scc1 .LBB%d_2" % i, ".LBB%d_2:" % i, "\ts_endpgm",
+                ".Lfunc_end%d:" % i, "\t.size\t%s, .Lfunc_end%d-%s" % (k, i, k), "\t.section\t.rodata",
+                "\t.amdhsa_kernel %s" % k, "\t\t.amdhsa_next_free_vgpr 3", "\t.end_amdhsa_kernel", "\t.text",
+                "; NumVgprs: 3"]
+    out += ["\t.type\t__hip_cuid_%s,@object" % cuid, "__hip_cuid_%s:" % cuid, "\t.amdgpu_metadata", "---",
+            "amdhsa.kernels:"]
+    for k in order:
+        out += ["  - .agpr_count:     0", "    .name:           %s" % k, "    .symbol:         %s.kd" % k,
+                "    .vgpr_count:     3"]
+    out += ["amdhsa.version:", "  - 1", "...", "\t.end_amdgpu_metadata"]
+    return "\n".join(out) + "\n"
+
+
+def test_listing_diff_compares_per_symbol():
+    """tools/listing_diff.py: kernels that change their order in the file (and with it the function
+    index of their labels) and the compilation unit's id compare equal; one changed instruction is
+    reported for its kernel alone."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        import listing_diff
+    finally:
+        sys.path.pop(0)
+    a = _listing(["kern_a", "kern_b"], "1111")
+    report, n = listing_diff.compare(a, _listing(["kern_b", "kern_a"], "2222"), 0)
+    assert report == [] and n >= 4   # two kernels, their metadata entries, the file's head
+    report, _ = listing_diff.compare(a, _listing(["kern_a", "kern_b"], "1111", "v_sub_u32_e32 v0, v1, v2"), 0)
+    assert len(report) == 1 and "kern_b" in report[0] and "differs" in report[0]
+    report, _ = listing_diff.compare(a, _listing(["kern_a"], "1111"), 0)
+    assert any("only in THIS" in r and "kern_b" in r for r in report)

@@ -36,7 +36,7 @@ LDS_CYC = {"ds_read_b32": 2, "ds_read_b64": 2, "ds_read_b128": 4, "ds_read_b96":
            "ds_write_b96": 10, "ds_write_b128": 13, "ds_swizzle_b32": 2, "ds_bpermute_b32": 2,
            "ds_permute_b32": 2, "ds_read_u8": 2, "ds_read_u16": 2, "ds_write_b8": 4, "ds_write_b16": 4}
 
-# segment names of the stamp sites (step_kernels.h pbn_rollout_pipe)
+# segment names of the stamp sites (rollout_pipe.h pbn_rollout_pipe, rollout_settle.h pbn_rollout_settle)
 SEGMENTS = {
     "state_fast": {"P0": "slot reads + obs store", "A15": "transpose to bit planes + plane store",
                    "A3": "input gathers + mux chains", "A12": "back-transpose",
@@ -64,10 +64,10 @@ KERNELS = {"pipe": ("pbn_rollout_pipe<%(W)d, %(B)d, false>",
                       lambda a: {"settle_state": a.K, "settle_sel": 2 * (a.K - 1) + a.pk, "settle_env_fast": a.W})}
 
 
-def compile_listing(inst, out_s):
+def compile_listing(inst, out_s, root=ROOT):
     src = os.path.join(tempfile.mkdtemp(prefix="isa_budget_"), "kernel.hip")
     with open(src, "w") as f:
-        f.write('#include "%s"\n' % os.path.join(ROOT, "pbn_rl_amd", "csrc", "step_kernels.h"))
+        f.write('#include "%s"\n' % os.path.join(root, "pbn_rl_amd", "csrc", "step_kernels.h"))
         f.write("void* isa_budget_instance() { return reinterpret_cast<void*>(&%s); }\n" % inst)
     subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-DPBN_ISA_MARKS",
                     "--offload-device-only", "-S", "-o", out_s, src], check=True,

@@ -18,7 +18,7 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 STAMP_LIB = os.path.join(ROOT, "pbn_rl_amd", "libpbn_env_stamps.so")
 PHASES = ["tables+barrier", "philox", "per-env", "transpose+S", "node eval", "back-transpose", "epilogue"]
-ROW = 32   # stamp words per block (pipelined kernel) or per wave (wave kernel), step_kernels.h PBN_PSTAMP
+ROW = 32   # stamp words per block (pipelined kernel) or per wave (wave kernel), step_debug.h PBN_PSTAMP
 
 
 def segments(full, it):
@@ -62,7 +62,7 @@ SETTLE_ROLES = {
 
 
 def settle_segments(full, it):
-    """pbn_rollout_settle's per-role segments of iteration kSettleStampIt (step_kernels.h)."""
+    """pbn_rollout_settle's per-role segments of iteration kSettleStampIt (rollout_settle.h)."""
     import numpy as np
     med = lambda x: int(np.median(x))
     c = lambda i: full[:, i]
