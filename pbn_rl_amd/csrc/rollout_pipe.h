@@ -321,9 +321,11 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
         // part 1: the draws that feed LDS reads, and the reads themselves
         uint32_t xhi = E.w, xlo = E.z;
         const uint32_t c_act = ext64(xhi, xlo, n1 * n1 * n1);
-        const uint32_t u2 = (uint32_t)((((((uint64_t)E.w) << 32) | E.z) * a.x_mult) >> 32);
         const uint32_t c = ext64(xhi, xlo, A * (A - 1));   // pair_draw (A >= 2), its halves apart
         const uint32_t as = pbn::pair_start(c, a.am1_magic);
+        // gap 2's uniform: what the two draws leave of X's top word (att_single: no third draw),
+        // hi32(X * x_mult) without a product of its own
+        const uint32_t u2 = xhi;
         uint32_t rs[W];
 #pragma unroll
         for (int w = 0; w < W; ++w) rs[w] = att_words[(size_t)as * W + w];   // (att_single: start_pick is `as`)

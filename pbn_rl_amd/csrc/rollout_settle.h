@@ -283,12 +283,13 @@ pbn_rollout_settle(StepArgs a) {
       const uint32_t c2 = first ? (pbn::kStreamEnv << 28) : ((pbn::kStreamSettleEnv << 28) | ((k - 1) << 8));
       const Word4 E = pbn::philox(ge_lo, st_lo, c2, ge_hi, u_k0, u_k1);
       // the step's draws from X = ENV words 3:2 (used where k = 0): actions, the autoreset pair,
-      // gap 2's uniform (X * x_mult, off the draws' chain)
+      // gap 2's uniform (what the two draws leave of X's top word, hi32(X * x_mult); att_single:
+      // no third draw)
       uint32_t xhi = E.w, xlo = E.z;
       const uint32_t c_act = ext64(xhi, xlo, n1 * n1 * n1);
       const uint32_t c = ext64(xhi, xlo, A * (A - 1));   // pair_draw (A >= 2), its halves apart
       const uint32_t as = pbn::pair_start(c, a.am1_magic);
-      const uint32_t u2 = first ? (uint32_t)((((((uint64_t)E.w) << 32) | E.z) * a.x_mult) >> 32) : E.z;
+      const uint32_t u2 = first ? xhi : E.z;
       uint32_t rs[W];
 #pragma unroll
       for (int w = 0; w < W; ++w) rs[w] = att_words[(size_t)as * W + w];

@@ -48,15 +48,16 @@ __host__ __device__ __forceinline__ void set_bit(uint32_t (&g)[W], int pos, int 
 
 // Three actions uniform on [0, N]: the base-(N+1) digits of c, one draw over (N+1)^3.
 // Division by N+1 is a multiply-high by magic = ceil(2^32 / (N+1)), exact for c * (N+1) < 2^32
-// (c < (N+1)^3 <= 129^3).
+// (c < (N+1)^3 <= 129^3).  Two divisions: the second quotient is below N+1 (c < (N+1)^3), so it is
+// the third digit itself, which the compiler cannot know (a third divide would always return 0).
 template <int W>
 __host__ __device__ __forceinline__ void actions_from_draw(uint32_t c, int N, uint32_t magic, uint32_t (&m)[W]) {
   const uint32_t n1 = (uint32_t)(N + 1);
+  const uint32_t q1 = mulhi32(c, magic), q2 = mulhi32(q1, magic);
+  const uint32_t acts[3] = {c - q1 * n1, q1 - q2 * n1, q2};
 #pragma unroll
   for (int q = 0; q < 3; ++q) {   // action a in [0, N]: 0 = no-op, else flip node a-1
-    const uint32_t qt = mulhi32(c, magic);
-    const int act = (int)(c - qt * n1);
-    c = qt;
+    const int act = (int)acts[q];
 #pragma unroll
     for (int w = 0; w < W; ++w)
       if (act > 0 && ((act - 1) >> 5) == w) m[w] |= 1u << ((act - 1) & 31);
@@ -67,14 +68,8 @@ __host__ __device__ __forceinline__ void actions_from_draw(uint32_t c, int N, ui
 // a = 0 shifts by 31 (the shift count's low five bits) onto a bit past the network that `vmask`
 // (valid_word_mask(N, 0)) clears once for all three: no per-action guard
 __host__ __device__ __forceinline__ uint32_t actions_mask31(uint32_t c, uint32_t n1, uint32_t magic, uint32_t vmask) {
-  uint32_t m = 0;
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const uint32_t qt = mulhi32(c, magic);
-    m |= 1u << ((c - qt * n1 - 1u) & 31u);
-    c = qt;
-  }
-  return m & vmask;
+  const uint32_t q1 = mulhi32(c, magic), q2 = mulhi32(q1, magic);   // (two divisions, as above)
+  return ((1u << ((c - q1 * n1 - 1u) & 31u)) | (1u << ((q1 - q2 * n1 - 1u) & 31u)) | (1u << ((q2 - 1u) & 31u))) & vmask;
 }
 
 // ---- the autoreset pair (reset_draw, first half): one draw c over the A(A-1) ordered (start,

@@ -1,8 +1,12 @@
 // Relative issue cost of the rollout kernel's VALU mix on gfx950: 8 independent chains per lane
 // of v_mad_u64_u32 (Philox products, bounded draws), v_bitop3_b32 (xor3, transposes, compares),
-// v_perm_b32 (mux-tree leaves) and v_mul_hi_u32, at full occupancy (8 waves per SIMD), timed with
-// HIP events.  Prints ns per wave-instruction per SIMD for each: the ratio to bitop3 is the cost
-// of one instruction in units of a full-rate op.
+// v_perm_b32 (mux-tree leaves), v_mul_hi_u32 and v_mul_lo_u32, and the 24-bit multiplies of the
+// bounded draws' divides (v_mul_hi_u32_u24, v_mul_u32_u24, v_mad_u32_u24, v_mad_i32_i24; written as
+// instructions: the compiler picks them only where it can prove the operands' ranges), at full
+// occupancy (8 waves per SIMD), timed with HIP events.  Prints ns per wave-instruction per SIMD for
+// each: the ratio to bitop3 is the cost of one instruction in units of a full-rate op.  (A chain
+// of high halves runs down to zero operands within a few links; the v_mul_lo_u32 chain keeps its
+// bits and reads the same.)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -23,8 +27,20 @@ __global__ void __launch_bounds__(256) rate_kernel(uint32_t* out, uint32_t seed)
         a[k] = __builtin_amdgcn_bitop3_b32(a[k], b[k], 0x1234567u, 0x96);
       } else if constexpr (OP == 2) {
         a[k] = __builtin_amdgcn_perm(a[k], b[k], 0x05040100u + it);
-      } else {
+      } else if constexpr (OP == 3) {
         a[k] = __umulhi(a[k], 0xCD9E8D57u) + b[k];
+      } else if constexpr (OP == 4) {
+        asm volatile("v_mul_hi_u32 %0, %0, %1" : "+v"(a[k]) : "v"(b[k]));
+      } else if constexpr (OP == 5) {
+        asm volatile("v_mul_lo_u32 %0, %0, %1" : "+v"(a[k]) : "v"(b[k]));
+      } else if constexpr (OP == 6) {
+        asm volatile("v_mul_hi_u32_u24 %0, %0, %1" : "+v"(a[k]) : "v"(b[k]));
+      } else if constexpr (OP == 7) {
+        asm volatile("v_mul_u32_u24 %0, %0, %1" : "+v"(a[k]) : "v"(b[k]));
+      } else if constexpr (OP == 8) {
+        asm volatile("v_mad_u32_u24 %0, %0, %1, %0" : "+v"(a[k]) : "v"(b[k]));
+      } else {
+        asm volatile("v_mad_i32_i24 %0, %0, %1, %0" : "+v"(a[k]) : "v"(b[k]));
       }
     }
   }
@@ -53,9 +69,12 @@ int main() {
   uint32_t* d;
   hipMalloc(&d, sizeof(uint32_t) * blocks * 256);
   const double insts_per_simd = (double)blocks * 4 / (cus * 4) * kIters * 8;   // wave-instructions per SIMD
-  const char* names[4] = {"v_mad_u64_u32", "v_bitop3_b32", "v_perm_b32", "v_mul_hi_u32 + v_add"};
-  float ms[4] = {run<0>(d, blocks), run<1>(d, blocks), run<2>(d, blocks), run<3>(d, blocks)};
-  for (int k = 0; k < 4; ++k)
+  constexpr int kOps = 10;
+  const char* names[kOps] = {"v_mad_u64_u32", "v_bitop3_b32", "v_perm_b32", "v_mul_hi_u32 + v_add", "v_mul_hi_u32",
+                             "v_mul_lo_u32", "v_mul_hi_u32_u24", "v_mul_u32_u24", "v_mad_u32_u24", "v_mad_i32_i24"};
+  float ms[kOps] = {run<0>(d, blocks), run<1>(d, blocks), run<2>(d, blocks), run<3>(d, blocks), run<4>(d, blocks),
+                    run<5>(d, blocks), run<6>(d, blocks), run<7>(d, blocks), run<8>(d, blocks), run<9>(d, blocks)};
+  for (int k = 0; k < kOps; ++k)
     printf("{\"op\": \"%s\", \"ms\": %.4f, \"ns_per_wave_inst_per_simd\": %.4f, \"vs_bitop3\": %.2f}\n", names[k], ms[k],
            ms[k] * 1e6 / insts_per_simd, ms[k] / ms[1]);
   hipFree(d);
