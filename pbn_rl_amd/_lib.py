@@ -1,4 +1,5 @@
-"""ctypes binding of libpbn_env.so (include/pbn_env.h).
+"""ctypes binding of libpbn_env.so, derived from include/pbn_env.h: the header's prototypes are
+the one description of the ABI (declared()), and load() binds from them.
 
 The HIP library is the only compute path: if it is missing or fails to load,
 every entry point raises -- there is no CPU fallback.
@@ -6,9 +7,11 @@ every entry point raises -- there is no CPU fallback.
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
+import re
 import subprocess
-from typing import Optional
+from typing import Dict, NamedTuple, Optional, Tuple
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libpbn_env.so")
@@ -24,17 +27,6 @@ FLAG_PERTURBED = 8
 FLAG_RESET = 16
 FLAG_UNSETTLED = 32
 
-EXPORTS = ["pbn_net_create", "pbn_net_destroy", "pbn_net_words", "pbn_reset", "pbn_step", "pbn_step_dev", "pbn_step_dev_store",
-           "pbn_rollout", "pbn_rollout_ex", "pbn_state_histogram", "pbn_obs_unpack", "pbn_bilinear_targets", "pbn_q_to_flipmask",
-           "pbn_q_to_flipmask_dev",
-           "pbn_heads_to_flipmask", "pbn_qnet_heads", "pbn_qnet_flipmask", "pbn_qnet_heads_from_state",
-           "pbn_qnet_flipmask_from_state", "pbn_replay_store", "pbn_replay_advance", "pbn_replay_batch", "pbn_bdq_td_loss", "pbn_bdq_layout", "pbn_bdq_learn_workspace",
-           "pbn_bdq_pack", "pbn_bdq_image_floats", "pbn_bdq_learn", "pbn_copy_async", "pbn_rollout_copy", "pbn_host_buffer", "pbn_host_buffer_free", "pbn_stream_sync",
-           "pbn_eval_track", "pbn_eval_reduce", "pbn_per_store", "pbn_per_sample", "pbn_per_update",
-           "pbn_bdq_td_loss_per", "pbn_bdq_learn_per", "pbn_dqn_layout", "pbn_dqn_image_floats", "pbn_dqn_pack",
-           "pbn_dqn_flipmask_from_state", "pbn_ddqn_learn_workspace", "pbn_ddqn_learn", "pbn_ddqn_schedule",
-           "pbn_rollout_dqn", "pbn_table_insert", "pbn_last_error",
-           "pbn_abi_version"]
 SOURCES = ["pbn_env.hip", "pbn_settle.hip", "pbn_agent.hip", "pbn_qnet.hip", "pbn_learn.hip", "pbn_eval.hip",
            "pbn_per.hip", "pbn_ddqn.hip", "pbn_table.hip"]
 
@@ -92,6 +84,79 @@ def build(verbose: bool = False, out: str = LIB_PATH, defines=()) -> str:
     return out
 
 
+class Decl(NamedTuple):
+    """One entry point as include/pbn_env.h declares it."""
+    restype: object     # a ctypes type, or None for void
+    argtypes: tuple     # one ctypes type per parameter
+    params: tuple       # the parameters' names
+    ctext: tuple        # the parameters as the header spells them, e.g. "const uint64_t* d_step"
+
+
+_SCALARS = {"int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "int32_t": ctypes.c_int32,
+            "uint32_t": ctypes.c_uint32, "float": ctypes.c_float, "double": ctypes.c_double, "int": ctypes.c_int}
+
+
+def _ctype(ctext: str, what: str, returns: bool = False):
+    """The binding's rule: any pointer is a c_void_p (a returned const char* a c_char_p), a scalar
+    its ctypes twin; anything else is an error that names ``what``."""
+    words = [w for w in ctext.replace("*", " * ").split() if w != "const"]
+    if "*" in words:
+        return ctypes.c_char_p if returns and words == ["char", "*"] else ctypes.c_void_p
+    if returns and words == ["void"]:
+        return None
+    if len(words) != 1 or words[0] not in _SCALARS:
+        raise PbnError(f"pbn_env.h: {what} has a type the binding does not know: '{ctext}'")
+    return _SCALARS[words[0]]
+
+
+def parse_header(text: str) -> Tuple[Dict[str, Decl], int]:
+    """({function: Decl}, PBN_ABI_VERSION) of a header's text.  Every statement with a parameter
+    list must parse as a prototype: a declaration is never dropped silently."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    version = re.search(r"^[ \t]*#[ \t]*define[ \t]+PBN_ABI_VERSION[ \t]+(\d+)", text, re.M)
+    if not version:
+        raise PbnError("pbn_env.h: PBN_ABI_VERSION is not defined")
+    text = re.sub(r"^[ \t]*#[^\n]*", " ", text, flags=re.M)    # preprocessor lines
+    text = re.sub(r'extern\s+"C"\s*\{', " ", text)
+    text = re.sub(r"\{[^{}]*\}", " ", text)                    # struct bodies
+    out: Dict[str, Decl] = {}
+    for stmt in text.split(";"):
+        if "(" not in stmt:
+            continue
+        m = re.fullmatch(r"\s*([\w\s*]+?)\s*\b(\w+)\s*\(([^()]*)\)\s*", stmt)
+        if not m:
+            raise PbnError(f"pbn_env.h: cannot parse '{' '.join(stmt.split())}'")
+        ret, name, plist = m.groups()
+        ctext = tuple(" ".join(p.split()) for p in plist.split(","))
+        if ctext in (("void",), ("",)):
+            ctext = ()
+        names, argtypes = [], []
+        for p in ctext:
+            pm = re.fullmatch(r"(.*?)\b(\w+)", p)
+            if not pm or not pm.group(1).strip():
+                raise PbnError(f"pbn_env.h: {name}: cannot parse parameter '{p}'")
+            names.append(pm.group(2))
+            argtypes.append(_ctype(pm.group(1), f"{name}: parameter {pm.group(2)}"))
+        out[name] = Decl(_ctype(ret, f"{name}: the return value", returns=True), tuple(argtypes), tuple(names), ctext)
+    return out, int(version.group(1))
+
+
+@functools.lru_cache(maxsize=None)
+def _header() -> Tuple[Dict[str, Decl], int]:
+    with open(os.path.join(INCLUDE_DIR, "pbn_env.h")) as f:
+        return parse_header(f.read())
+
+
+def declared() -> Dict[str, Decl]:
+    """The C ABI, {function: Decl}, read once from include/pbn_env.h: the one description that
+    load() binds from."""
+    return _header()[0]
+
+
+EXPORTS = list(declared())
+ABI_VERSION = _header()[1]     # PBN_ABI_VERSION of the header
+
+
 def load() -> ctypes.CDLL:
     global _lib
     if _lib is not None:
@@ -100,140 +165,14 @@ def load() -> ctypes.CDLL:
     if not os.path.exists(path):
         raise PbnError(f"{path} not built: run `python -c 'import __graft_entry__ as g; g.build()'`")
     L = ctypes.CDLL(path)
-    vp, u64, i64, u32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint32
-    L.pbn_net_create.argtypes = [vp, ctypes.POINTER(vp)]
-    L.pbn_net_create.restype = ctypes.c_int
-    L.pbn_net_destroy.argtypes = [vp]
-    L.pbn_net_destroy.restype = ctypes.c_int
-    L.pbn_net_words.argtypes = [vp]
-    L.pbn_net_words.restype = ctypes.c_int
-    L.pbn_reset.argtypes = [vp, u64, u64, u64, i64, vp, vp, vp, vp]
-    L.pbn_reset.restype = ctypes.c_int
-    L.pbn_step.argtypes = [vp, u64, u64, u64, i64, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.pbn_step.restype = ctypes.c_int
-    L.pbn_step_dev.argtypes = [vp, u64, vp, u64, i64, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.pbn_step_dev.restype = ctypes.c_int
-    if hasattr(L, "pbn_step_dev_store"):   # (ABI 11)
-        L.pbn_step_dev_store.argtypes = [vp, u64, vp, u64, i64, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.pbn_step_dev_store.restype = ctypes.c_int
-    L.pbn_rollout.argtypes = [vp, u64, u64, u64, i64, ctypes.c_int32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.pbn_rollout.restype = ctypes.c_int
-    L.pbn_rollout_ex.argtypes = [vp, u64, u64, u64, i64, ctypes.c_int32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                 vp]
-    L.pbn_rollout_ex.restype = ctypes.c_int
-    L.pbn_state_histogram.argtypes = [vp, i64, i64, i64, ctypes.c_int32, vp, vp]
-    L.pbn_state_histogram.restype = ctypes.c_int
-    L.pbn_obs_unpack.argtypes = [vp, i64, vp, vp, vp, vp]
-    L.pbn_obs_unpack.restype = ctypes.c_int
-    L.pbn_bilinear_targets.argtypes = [vp, i64, vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
-                                       vp, vp]
-    L.pbn_bilinear_targets.restype = ctypes.c_int
-    L.pbn_q_to_flipmask.argtypes = [vp, u64, u64, u64, i64, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_float,
-                                    vp, vp, vp]
-    L.pbn_q_to_flipmask.restype = ctypes.c_int
-    L.pbn_q_to_flipmask_dev.argtypes = [vp, u64, vp, u64, i64, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_float,
-                                        vp, vp, vp, vp]
-    L.pbn_q_to_flipmask_dev.restype = ctypes.c_int
-    L.pbn_heads_to_flipmask.argtypes = [vp, u64, u64, vp, u64, i64, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_float,
-                                        vp, vp, vp, vp]
-    L.pbn_heads_to_flipmask.restype = ctypes.c_int
-    L.pbn_qnet_heads.argtypes = [vp, i64] + [vp] * 11 + [ctypes.c_int32, ctypes.c_int32, ctypes.c_float, vp, vp]
-    L.pbn_qnet_heads.restype = ctypes.c_int
-    L.pbn_qnet_flipmask.argtypes = ([vp, u64, u64, vp, u64, i64] + [vp] * 11 +
-                                    [ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp])
-    L.pbn_qnet_flipmask.restype = ctypes.c_int
-    L.pbn_qnet_heads_from_state.argtypes = [vp, i64] + [vp] * 14 + [ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
-                                                                     vp, vp]
-    L.pbn_qnet_heads_from_state.restype = ctypes.c_int
-    L.pbn_qnet_flipmask_from_state.argtypes = ([vp, u64, u64, vp, u64, i64] + [vp] * 14 +
-                                               [ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_float,
-                                                vp, vp, vp, vp])
-    L.pbn_qnet_flipmask_from_state.restype = ctypes.c_int
-    L.pbn_last_error.argtypes = []
-    L.pbn_last_error.restype = ctypes.c_char_p
-    L.pbn_replay_store.argtypes = ([i64, vp, i64, ctypes.c_int32, ctypes.c_int32] + [vp] * 6 + [u32, vp] + [vp] * 6 +
-                                   [vp] * 4 + [vp])
-    L.pbn_replay_store.restype = ctypes.c_int
-    L.pbn_replay_batch.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp]
-    L.pbn_replay_batch.restype = ctypes.c_int
-    L.pbn_bdq_td_loss.argtypes = [vp, vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
-                                  vp, vp, vp, vp]
-    L.pbn_bdq_td_loss.restype = ctypes.c_int
-    i32, f32 = ctypes.c_int32, ctypes.c_float
-    if hasattr(L, "pbn_bdq_learn"):   # (diagnostic builds of older revisions predate the fused update)
-        L.pbn_replay_advance.argtypes = [i64, i64, vp, vp, vp, vp, vp, ctypes.c_double, ctypes.c_double, i64, u64,
-                                         vp, vp, vp]
-        L.pbn_replay_advance.restype = ctypes.c_int
-        L.pbn_bdq_layout.argtypes = [i32, i32, vp]
-        L.pbn_bdq_layout.restype = ctypes.c_int
-        L.pbn_bdq_learn_workspace.argtypes = [i32, i32, i64, vp]
-        L.pbn_bdq_learn_workspace.restype = ctypes.c_int
-        L.pbn_bdq_pack.argtypes = [vp, i32, vp, vp, vp]
-        L.pbn_bdq_pack.restype = ctypes.c_int
-        if hasattr(L, "pbn_bdq_image_floats"):   # (ABI 10)
-            L.pbn_bdq_image_floats.argtypes = [vp, i32, vp]
-            L.pbn_bdq_image_floats.restype = ctypes.c_int
-        L.pbn_bdq_learn.argtypes = ([vp, i64, vp, i64, vp, vp, vp, vp, i32, vp, vp] + [vp] * 7 + [f32] * 7 +
-                                    [vp, i64, vp, vp, vp, vp])
-        L.pbn_bdq_learn.restype = ctypes.c_int
-    L.pbn_copy_async.argtypes = [vp, vp, i64, vp]
-    L.pbn_copy_async.restype = ctypes.c_int
-    L.pbn_rollout_copy.argtypes = [vp, u64, u64, u64, i64, ctypes.c_int32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                   vp, vp, i64, vp]
-    L.pbn_rollout_copy.restype = ctypes.c_int
-    if hasattr(L, "pbn_host_buffer"):   # (ABI 9)
-        L.pbn_host_buffer.argtypes = [i64, ctypes.POINTER(vp), ctypes.POINTER(vp)]
-        L.pbn_host_buffer.restype = ctypes.c_int
-        L.pbn_host_buffer_free.argtypes = [vp]
-        L.pbn_host_buffer_free.restype = ctypes.c_int
-        L.pbn_stream_sync.argtypes = [vp]
-        L.pbn_stream_sync.restype = ctypes.c_int
-    if hasattr(L, "pbn_eval_track"):   # (additive exports of ABI 11: the control evaluation)
-        L.pbn_eval_track.argtypes = [i64, i64, i32, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.pbn_eval_track.restype = ctypes.c_int
-        L.pbn_eval_reduce.argtypes = [vp, i64, i64, i32, vp, vp, vp, vp]
-        L.pbn_eval_reduce.restype = ctypes.c_int
-    if hasattr(L, "pbn_per_store"):   # (additive exports of ABI 11: prioritised replay)
-        f64 = ctypes.c_double
-        L.pbn_per_store.argtypes = [i64, vp, i64, i64, f64, vp, vp, vp, vp]
-        L.pbn_per_store.restype = ctypes.c_int
-        L.pbn_per_sample.argtypes = [i32, i64, i64, vp, vp, vp, vp, f64, f64, u64, vp, vp, vp, vp]
-        L.pbn_per_sample.restype = ctypes.c_int
-        L.pbn_per_update.argtypes = [i32, i64, i64, f64, vp, vp, vp, vp, vp, vp, vp]
-        L.pbn_per_update.restype = ctypes.c_int
-        L.pbn_bdq_td_loss_per.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp]
-        L.pbn_bdq_td_loss_per.restype = ctypes.c_int
-    if hasattr(L, "pbn_bdq_learn_per"):   # (additive export of ABI 11: the fused update on a prioritised batch)
-        L.pbn_bdq_learn_per.argtypes = ([vp, i64, vp, i64, vp, vp, vp, vp, i32, vp, vp] + [vp] * 7 + [f32] * 7 +
-                                        [vp, i64, vp, vp, vp, f32, vp, vp, vp])
-        L.pbn_bdq_learn_per.restype = ctypes.c_int
-    if hasattr(L, "pbn_ddqn_learn"):   # (additive exports of ABI 11: the DDQN / DDQNPER agent)
-        L.pbn_dqn_layout.argtypes = [i32, i32, i32, vp]
-        L.pbn_dqn_layout.restype = ctypes.c_int
-        L.pbn_dqn_image_floats.argtypes = [vp, i32, i32, vp]
-        L.pbn_dqn_image_floats.restype = ctypes.c_int
-        L.pbn_dqn_pack.argtypes = [vp, i32, i32, vp, vp, vp]
-        L.pbn_dqn_pack.restype = ctypes.c_int
-        L.pbn_dqn_flipmask_from_state.argtypes = [vp, u64, u64, vp, u64, i64, vp, vp, i32, i32, vp, f32, vp, vp, vp,
-                                                  vp, vp]
-        L.pbn_dqn_flipmask_from_state.restype = ctypes.c_int
-        L.pbn_ddqn_learn_workspace.argtypes = [i32, i32, i32, i64, vp]
-        L.pbn_ddqn_learn_workspace.restype = ctypes.c_int
-        L.pbn_ddqn_learn.argtypes = ([vp, i32, i32, i64, vp, i64] + [vp] * 6 + [vp] * 6 + [f32] * 6 +
-                                     [vp, i64, vp, vp, vp, vp, f32, vp, vp])
-        L.pbn_ddqn_learn.restype = ctypes.c_int
-    if hasattr(L, "pbn_ddqn_schedule"):   # (additive export of ABI 11: the captured DDQN frame's schedule step)
-        L.pbn_ddqn_schedule.argtypes = [vp, ctypes.c_double, vp, i64, i64, vp, vp, i64, vp, vp, i64, vp]
-        L.pbn_ddqn_schedule.restype = ctypes.c_int
-    if hasattr(L, "pbn_rollout_dqn"):   # (additive export of ABI 11: the policy rollout)
-        L.pbn_rollout_dqn.argtypes = [vp, u64, u64, u64, i64, i32, u32, vp, vp, vp, i32, i32, vp, f32, vp, vp, vp, vp,
-                                      vp, vp, vp, vp]
-        L.pbn_rollout_dqn.restype = ctypes.c_int
-    if hasattr(L, "pbn_table_insert"):   # (additive export of ABI 11: the visited-state hash table)
-        L.pbn_table_insert.argtypes = [vp, i64, i64, i64, i32, i32, vp, i64, vp, vp, vp, vp, vp, u32, vp]
-        L.pbn_table_insert.restype = ctypes.c_int
-    L.pbn_abi_version.argtypes = []
-    L.pbn_abi_version.restype = ctypes.c_int
+    for name, d in declared().items():
+        if hasattr(L, name):   # (a diagnostic build of an older revision lacks the later exports)
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = d.restype, list(d.argtypes)
+    want, got = ABI_VERSION, L.pbn_abi_version() if hasattr(L, "pbn_abi_version") else None
+    if got != want:
+        raise PbnError(f"{path} has ABI version {got}, include/pbn_env.h declares {want}: rebuild with "
+                       "`python -c 'import __graft_entry__ as g; g.build()'`")
     _lib = L
     return L
 

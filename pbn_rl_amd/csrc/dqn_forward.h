@@ -10,6 +10,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "host_check.h"
 #include "wave_util.h"
 
 namespace {
@@ -19,7 +20,8 @@ constexpr int kMaxA = 128;      // N + 1 <= 128
 
 enum Seg { BIL_W, BIL_B, L1_W, L1_B, OUT_W, OUT_B, TOTAL };
 
-inline int64_t al16(int64_t x) { return (x + 15) & ~int64_t(15); }
+using pbn::al16;
+using pbn::explore_threshold;
 
 // Shapes, the parameter layout (pbn_dqn_layout) and the image layout.  Image (floats):
 //   T     [n_attr][N][H0p]   the bilinear layer contracted with each attractor's first state,
@@ -77,12 +79,6 @@ inline void make_dims(int N, int W, int n_attr, int h0, int h1, Dims* d) {
   d->iw2f = i;
   i += (int64_t)d->Ap * d->H1p;
   d->itotal = i;
-}
-
-// EXPLORE law (DESIGN.md "Step semantics" 6): explore iff word 0 < floor(epsilon 2^32), so
-// epsilon = 1 always explores and 0 never does
-__host__ __device__ inline uint64_t explore_threshold(float epsilon) {
-  return (uint64_t)floor((double)epsilon * 4294967296.0);
 }
 
 // ---- the forward of 16 rows on one wave --------------------------------------------------------

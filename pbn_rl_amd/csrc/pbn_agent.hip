@@ -22,6 +22,7 @@
 #include <algorithm>
 
 #include "../../include/pbn_env.h"
+#include "host_check.h"
 #include "net_view.h"
 #include "philox.h"
 #include "replay_draw.h"
@@ -357,8 +358,6 @@ __global__ void __launch_bounds__(kQEnvs * kMaxBranches) q_to_flipmask_kernel(
   }
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 }  // namespace
 
 // ---- n transitions into the replay ring in one pass (pbn_replay_store): env e goes to slot
@@ -588,7 +587,7 @@ int pbn_obs_unpack(const pbn_net* net, int64_t n_envs, const uint32_t* d_state, 
   if ((int64_t)n_envs * v.n_nodes >= ((int64_t)1 << 31)) return pbn::set_error(PBN_EINVAL, "n_envs * n_nodes >= 2^31");
   if (n_envs == 0) return PBN_OK;
   if (!d_state || !d_target || !d_obs) return pbn::set_error(PBN_EINVAL, "null buffer");
-  if (!aligned16(d_obs)) return pbn::set_error(PBN_EINVAL, "d_obs must be 16-byte aligned");
+  if (!pbn::aligned(d_obs, 16)) return pbn::set_error(PBN_EINVAL, "d_obs must be 16-byte aligned");
   const int64_t total4 = n_envs * v.n_nodes / 4;
   const unsigned blocks = (unsigned)std::min<int64_t>((total4 + kObsThreads - 1) / kObsThreads, 8192);
   hipLaunchKernelGGL(obs_unpack_kernel, dim3(blocks), dim3(kObsThreads), 0, (hipStream_t)stream, d_state, d_target,
@@ -610,7 +609,7 @@ int pbn_bilinear_targets(const pbn_net* net, int64_t n_envs, const uint32_t* d_s
   if (out_dim < 4 || out_dim > 1024 || (out_dim & 3)) return pbn::set_error(PBN_EINVAL, "out_dim must be a multiple of 4 in 4..1024");
   if (n_envs == 0) return PBN_OK;
   if (!d_state || !d_target || !d_bias || !d_y || (v.n_attr > 0 && !d_T)) return pbn::set_error(PBN_EINVAL, "null buffer");
-  if (!aligned16(d_bias) || !aligned16(d_y) || (d_T && !aligned16(d_T)))
+  if (!pbn::aligned(d_bias, 16) || !pbn::aligned(d_y, 16) || (d_T && !pbn::aligned(d_T, 16)))
     return pbn::set_error(PBN_EINVAL, "d_T, d_bias and d_y must be 16-byte aligned");
   const uint32_t n = (uint32_t)n_envs;
   // the LDS-staged kernel when both table slices fit (A N <= 556 rows: Bittner-28's 14 x 28 and
@@ -670,12 +669,11 @@ static int q_to_flipmask_impl(const pbn_net* net, uint64_t seed, uint64_t step, 
     return pbn::set_error(PBN_EINVAL, "n_envs and env_offset must be multiples of 32");
   if (n_branches < 1 || n_branches > kMaxBranches) return pbn::set_error(PBN_EINVAL, "n_branches must be 1..7");
   if (n_actions != v.n_nodes + 1) return pbn::set_error(PBN_EINVAL, "n_actions must be n_nodes + 1");
-  if (!(epsilon >= 0.f && epsilon <= 1.f)) return pbn::set_error(PBN_EINVAL, "epsilon must be in [0, 1]");
+  if (const char* msg = pbn::explore_args_error(epsilon)) return pbn::set_error(PBN_EINVAL, msg);
   if (n_envs == 0) return PBN_OK;
   if (!d_q || !d_flipmask) return pbn::set_error(PBN_EINVAL, "null buffer");
-  if (!aligned16(d_q)) return pbn::set_error(PBN_EINVAL, "d_q must be 16-byte aligned");
-  // explore iff word 0 < floor(epsilon * 2^32): epsilon = 1 always explores, 0 never
-  const uint64_t eps_u = (uint64_t)floor((double)epsilon * 4294967296.0);
+  if (!pbn::aligned(d_q, 16)) return pbn::set_error(PBN_EINVAL, "d_q must be 16-byte aligned");
+  const uint64_t eps_u = pbn::explore_threshold(epsilon);
   const size_t lds = (size_t)kQEnvs * (n_branches + heads) * n_actions * sizeof(float) +
                     (size_t)kQEnvs * n_branches * sizeof(int);
   if (lds > 160 * 1024) return pbn::set_error(PBN_EINVAL, "n_branches * n_actions too large");
@@ -707,9 +705,7 @@ int pbn_q_to_flipmask(const pbn_net* net, uint64_t seed, uint64_t step, uint64_t
 int pbn_q_to_flipmask_dev(const pbn_net* net, uint64_t seed, const uint64_t* d_step, uint64_t env_offset,
                           int64_t n_envs, int32_t n_branches, int32_t n_actions, const float* d_q, float epsilon,
                           const float* d_epsilon, uint32_t* d_flipmask, int32_t* d_actions, void* stream) {
-  if (!d_step) return pbn::set_error(PBN_EINVAL, "null d_step");
-  if (((uintptr_t)d_step & 7u) != 0) return pbn::set_error(PBN_EINVAL, "d_step must be 8-byte aligned");
-  if (d_epsilon && ((uintptr_t)d_epsilon & 3u) != 0) return pbn::set_error(PBN_EINVAL, "d_epsilon misaligned");
+  if (const char* msg = pbn::dev_scalars_error(d_step, d_epsilon, true)) return pbn::set_error(PBN_EINVAL, msg);
   return q_to_flipmask_impl(net, seed, 0, d_step, env_offset, n_envs, n_branches, n_actions, d_q, epsilon,
                             d_epsilon, d_flipmask, d_actions, stream);
 }
@@ -718,8 +714,7 @@ int pbn_heads_to_flipmask(const pbn_net* net, uint64_t seed, uint64_t step, cons
                           uint64_t env_offset, int64_t n_envs, int32_t n_branches, int32_t n_actions,
                           const float* d_heads, float epsilon, const float* d_epsilon, uint32_t* d_flipmask,
                           int32_t* d_actions, void* stream) {
-  if (d_step && ((uintptr_t)d_step & 7u) != 0) return pbn::set_error(PBN_EINVAL, "d_step must be 8-byte aligned");
-  if (d_epsilon && ((uintptr_t)d_epsilon & 3u) != 0) return pbn::set_error(PBN_EINVAL, "d_epsilon misaligned");
+  if (const char* msg = pbn::dev_scalars_error(d_step, d_epsilon)) return pbn::set_error(PBN_EINVAL, msg);
   return q_to_flipmask_impl(net, seed, step, d_step, env_offset, n_envs, n_branches, n_actions, d_heads, epsilon,
                             d_epsilon, d_flipmask, d_actions, stream, 1);
 }
@@ -817,7 +812,7 @@ int pbn_bdq_td_loss_per(const float* d_online, const float* d_target, const int6
     return pbn::set_error(PBN_EINVAL, "null buffer");
   if ((((uintptr_t)d_online | (uintptr_t)d_target | (uintptr_t)d_rewards | (uintptr_t)d_masks | (uintptr_t)d_weights |
         (uintptr_t)d_loss | (uintptr_t)d_grad | (uintptr_t)d_priority | (uintptr_t)d_scratch) & 3u) != 0 ||
-      ((uintptr_t)d_actions & 7u) != 0)
+      !pbn::aligned(d_actions, 8))
     return pbn::set_error(PBN_EINVAL, "float buffers must be 4-byte, d_actions 8-byte aligned");
   const int blocks = (batch + kTdRows - 1) / kTdRows;
   const int H = n_branches + 1;

@@ -40,6 +40,7 @@
 
 #include "../../include/pbn_env.h"
 #include "dqn_forward.h"
+#include "host_check.h"
 #include "net_view.h"
 #include "philox.h"
 
@@ -525,8 +526,6 @@ __global__ void __launch_bounds__(256) ddqn_schedule_kernel(ScheduleArgs a) {
   }
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 bool overlap(const void* p, const void* q, int64_t bytes) {
   const char* a = static_cast<const char*>(p);
   const char* b = static_cast<const char*>(q);
@@ -577,7 +576,7 @@ int pbn_dqn_pack(const pbn_net* net, int32_t h0, int32_t h1, const float* d_para
   Dims d;
   if (int rc = net_dims(net, h0, h1, &d)) return rc;
   if (!d_params || !d_image) return pbn::set_error(PBN_EINVAL, "null buffer");
-  if (!aligned16(d_params) || !aligned16(d_image))
+  if (!pbn::aligned(d_params, 16) || !pbn::aligned(d_image, 16))
     return pbn::set_error(PBN_EINVAL, "parameter and image buffers: 16-byte aligned");
   if (int rc = pbn::check_device(net)) return rc;
   pbn::NetView nv;
@@ -594,14 +593,12 @@ int pbn_dqn_flipmask_from_state(const pbn_net* net, uint64_t seed, uint64_t step
                                 float* d_q, uint32_t* d_flipmask, int32_t* d_actions, void* stream) {
   if (n_envs < 0 || (n_envs & 31) || (env_offset & 31))
     return pbn::set_error(PBN_EINVAL, "n_envs and env_offset must be multiples of 32");
-  if (!(epsilon >= 0.f && epsilon <= 1.f)) return pbn::set_error(PBN_EINVAL, "epsilon must be in [0, 1]");
-  if (d_step && ((uintptr_t)d_step & 7u) != 0) return pbn::set_error(PBN_EINVAL, "d_step must be 8-byte aligned");
-  if (d_epsilon && ((uintptr_t)d_epsilon & 3u) != 0) return pbn::set_error(PBN_EINVAL, "d_epsilon misaligned");
+  if (const char* msg = pbn::explore_args_error(epsilon, d_step, d_epsilon)) return pbn::set_error(PBN_EINVAL, msg);
   ActArgs a;
   if (int rc = net_dims(net, h0, h1, &a.d)) return rc;
   if (n_envs * (int64_t)a.d.A >= ((int64_t)1 << 31)) return pbn::set_error(PBN_EINVAL, "n_envs * n_actions >= 2^31");
   if (!d_state || !d_target || !d_image || !d_flipmask) return pbn::set_error(PBN_EINVAL, "null buffer");
-  if (!aligned16(d_image)) return pbn::set_error(PBN_EINVAL, "d_image must be 16-byte aligned");
+  if (!pbn::aligned(d_image, 16)) return pbn::set_error(PBN_EINVAL, "d_image must be 16-byte aligned");
   if (((uintptr_t)d_q | (uintptr_t)d_flipmask | (uintptr_t)d_actions | (uintptr_t)d_state) & 3u)
     return pbn::set_error(PBN_EINVAL, "d_state, d_q, d_flipmask and d_actions must be 4-byte aligned");
   if (int rc = pbn::check_device(net)) return rc;
@@ -661,8 +658,8 @@ int pbn_ddqn_learn(const pbn_net* net, int32_t h0, int32_t h1, int64_t batch, co
   if (!d_image || !d_target_image) return pbn::set_error(PBN_EINVAL, "null network image");
   for (const void* p : {(const void*)d_params, (const void*)d_adam_m, (const void*)d_adam_v, (const void*)d_workspace,
                         (const void*)d_image, (const void*)d_target_image, (const void*)d_grad})
-    if (!aligned16(p)) return pbn::set_error(PBN_EINVAL, "parameter, image and workspace buffers: 16-byte aligned");
-  if (((uintptr_t)d_idx & 7u) || (((uintptr_t)d_state | (uintptr_t)d_next_state | (uintptr_t)d_action |
+    if (!pbn::aligned(p, 16)) return pbn::set_error(PBN_EINVAL, "parameter, image and workspace buffers: 16-byte aligned");
+  if (!pbn::aligned(d_idx, 8) || (((uintptr_t)d_state | (uintptr_t)d_next_state | (uintptr_t)d_action |
                                    (uintptr_t)d_reward | (uintptr_t)d_adam_step | (uintptr_t)d_loss |
                                    (uintptr_t)d_grad_norm) & 3u))
     return pbn::set_error(PBN_EINVAL, "d_idx must be 8-byte, the ring and scalar buffers 4-byte aligned");
@@ -722,7 +719,8 @@ int pbn_ddqn_schedule(double* d_beta, double beta_increment, const int64_t* d_st
     return pbn::set_error(PBN_EINVAL, "pbn_ddqn_schedule: n_params and n_image must be positive multiples of 4");
   if (!d_target_params || !d_params || !d_target_image || !d_image)
     return pbn::set_error(PBN_EINVAL, "pbn_ddqn_schedule: null buffer");
-  if (!aligned16(d_target_params) || !aligned16(d_params) || !aligned16(d_target_image) || !aligned16(d_image))
+  if (!pbn::aligned(d_target_params, 16) || !pbn::aligned(d_params, 16) || !pbn::aligned(d_target_image, 16) ||
+      !pbn::aligned(d_image, 16))
     return pbn::set_error(PBN_EINVAL, "pbn_ddqn_schedule: parameter and image buffers: 16-byte aligned");
   if (overlap(d_target_params, d_params, n_params * 4) || overlap(d_target_image, d_image, n_image * 4))
     return pbn::set_error(PBN_EINVAL, "pbn_ddqn_schedule: a target buffer overlaps its source");

@@ -30,6 +30,7 @@
 
 #include "../../include/pbn_env.h"
 #include "bitslice.h"
+#include "host_check.h"
 #include "net_image.h"
 #include "net_view.h"
 #include "philox.h"
@@ -335,7 +336,7 @@ int pbn_copy_async(void* d_dst, const void* d_src, int64_t bytes, void* stream) 
   if (bytes < 0) return fail(PBN_EINVAL, "bytes < 0");
   if (bytes == 0) return PBN_OK;
   if (!d_dst || !d_src) return fail(PBN_EINVAL, "null buffer");
-  if ((bytes & 15) || ((uintptr_t)d_dst & 15u) || ((uintptr_t)d_src & 15u))
+  if ((bytes & 15) || !pbn::aligned(d_dst, 16) || !pbn::aligned(d_src, 16))
     return fail(PBN_EINVAL, "pointers and bytes must be 16-byte aligned");
   const char* d = static_cast<const char*>(d_dst);
   const char* s = static_cast<const char*>(d_src);
@@ -405,8 +406,6 @@ static int check_common(pbn_net* net, uint64_t env_offset, int64_t n_envs, bool 
   return PBN_OK;
 }
 
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 // The launch arguments every step kernel shares: the net's tables and encodings, the key and
 // the env range (the caller adds its buffers, mode and step count)
 static void fill_args(const pbn_net* net, StepArgs* a, uint64_t seed, uint64_t step, uint64_t env_offset,
@@ -459,10 +458,10 @@ static int step_impl(pbn_net* net, uint64_t seed, uint64_t step, const uint64_t*
     return fail(PBN_EINVAL, "null buffer");
   // (the ring form steps in place: the wave kernel's lane reads its env's state once, at entry)
   if (d_state_out == d_state && !ring) return fail(PBN_EINVAL, "d_state_out must not alias d_state");
-  if (!aligned16(d_state) || !aligned16(d_flipmask) || !aligned16(d_target) || !aligned16(d_t) ||
-      !aligned16(d_state_out) || !aligned16(d_reward) || !aligned16(d_flags) ||
-      (d_final_state && !aligned16(d_final_state)))
-    return fail(PBN_EINVAL, "device buffers must be 16-byte aligned");
+  for (const void* p : {(const void*)d_state, (const void*)d_flipmask, (const void*)d_target, (const void*)d_t,
+                        (const void*)d_state_out, (const void*)d_reward, (const void*)d_flags,
+                        (const void*)d_final_state})   // (d_final_state may be null)
+    if (!pbn::aligned(p, 16)) return fail(PBN_EINVAL, "device buffers must be 16-byte aligned");
   StepArgs a;
   fill_args(net, &a, seed, step, env_offset, n_envs);
   a.step_ptr = d_step;
@@ -480,7 +479,7 @@ static int step_impl(pbn_net* net, uint64_t seed, uint64_t step, const uint64_t*
     if (net->route.settle) return fail(PBN_EINVAL, "pbn_step_dev_store: the one-update law only (settle_max < 2)");
     if (r.capacity < n_envs) return fail(PBN_EINVAL, "pbn_ring_store: capacity < n_envs");
     if (r.n_branches < 1 || r.n_branches > kRingMaxK) return fail(PBN_EINVAL, "pbn_ring_store: n_branches 1..8");
-    if (!r.d_pos || ((uintptr_t)r.d_pos & 7u) || !r.d_state || !r.d_next_state || !r.d_target || !r.d_reward ||
+    if (!r.d_pos || !pbn::aligned(r.d_pos, 8) || !r.d_state || !r.d_next_state || !r.d_target || !r.d_reward ||
         !r.d_done || !r.d_action || !r.d_actions_in)
       return fail(PBN_EINVAL, "pbn_ring_store: null or misaligned buffer");
     a.r_state = r.d_state;
@@ -517,8 +516,7 @@ int pbn_step_dev(pbn_net* net, uint64_t seed, const uint64_t* d_step, uint64_t e
                  uint32_t mode, const uint32_t* d_state, uint32_t* d_flipmask, uint8_t* d_target, uint8_t* d_t,
                  uint32_t* d_state_out, uint32_t* d_final_state, float* d_reward, uint8_t* d_flags,
                  void* stream) {
-  if (!d_step) return fail(PBN_EINVAL, "null d_step");
-  if (((uintptr_t)d_step & 7u) != 0) return fail(PBN_EINVAL, "d_step must be 8-byte aligned");
+  if (const char* msg = pbn::dev_scalars_error(d_step, nullptr, true)) return fail(PBN_EINVAL, msg);
   return step_impl(net, seed, 0, d_step, env_offset, n_envs, mode, d_state, d_flipmask, d_target, d_t,
                    d_state_out, d_final_state, d_reward, d_flags, stream);
 }
@@ -527,8 +525,7 @@ int pbn_step_dev_store(pbn_net* net, uint64_t seed, const uint64_t* d_step, uint
                        uint32_t mode, uint32_t* d_state, uint32_t* d_flipmask, uint8_t* d_target, uint8_t* d_t,
                        uint32_t* d_final_state, float* d_reward, uint8_t* d_flags, const pbn_ring_store* ring,
                        void* stream) {
-  if (!d_step) return fail(PBN_EINVAL, "null d_step");
-  if (((uintptr_t)d_step & 7u) != 0) return fail(PBN_EINVAL, "d_step must be 8-byte aligned");
+  if (const char* msg = pbn::dev_scalars_error(d_step, nullptr, true)) return fail(PBN_EINVAL, msg);
   if (!ring) return fail(PBN_EINVAL, "null ring");
   return step_impl(net, seed, 0, d_step, env_offset, n_envs, mode, d_state, d_flipmask, d_target, d_t, d_state,
                    d_final_state, d_reward, d_flags, stream, ring);
@@ -638,18 +635,18 @@ int pbn_rollout_dqn(pbn_net* net, uint64_t seed, uint64_t step, uint64_t env_off
   if ((n_envs & 31) || (env_offset & 31)) return fail(PBN_EINVAL, "n_envs and env_offset must be multiples of 32");
   if (n_envs >= ((int64_t)1 << 30)) return fail(PBN_EINVAL, "n_envs must be below 2^30");
   if (const char* msg = shape_error(1, h0, h1)) return fail(PBN_EINVAL, msg);
-  if (!(epsilon >= 0.f && epsilon <= 1.f)) return fail(PBN_EINVAL, "epsilon must be in [0, 1]");
+  if (const char* msg = pbn::explore_args_error(epsilon)) return fail(PBN_EINVAL, msg);
   if (!net) return fail(PBN_EINVAL, "null net");
   if (const char* msg = shape_error(net->base.n_nodes, h0, h1)) return fail(PBN_EINVAL, msg);
   if (!net->dqn_kernel) return fail(PBN_EINVAL, "pbn_rollout_dqn: no kernel instance for this net");
   if (n_envs == 0 || n_steps == 0) return PBN_OK;
   if (!d_state || !d_target || !d_t || !d_image || !d_flipmask || !d_reward || !d_flags)
     return fail(PBN_EINVAL, "null buffer");
-  if (!aligned16(d_image)) return fail(PBN_EINVAL, "d_image must be 16-byte aligned");
+  if (!pbn::aligned(d_image, 16)) return fail(PBN_EINVAL, "d_image must be 16-byte aligned");
   if (((uintptr_t)d_state | (uintptr_t)d_flipmask | (uintptr_t)d_actions | (uintptr_t)d_obs |
        (uintptr_t)d_final_state | (uintptr_t)d_reward) & 3u)
     return fail(PBN_EINVAL, "32-bit device buffers must be 4-byte aligned");
-  if ((uintptr_t)d_updates & 1u) return fail(PBN_EINVAL, "d_updates must be 2-byte aligned");
+  if (!pbn::aligned(d_updates, 2)) return fail(PBN_EINVAL, "d_updates must be 2-byte aligned");
   if (int rc = pbn::check_device(net)) return rc;
   StepArgs a;
   fill_args(net, &a, seed, step, env_offset, n_envs);
@@ -685,7 +682,7 @@ int pbn_rollout_copy(pbn_net* net, uint64_t seed, uint64_t step, uint64_t env_of
   if (copy_bytes < 0) return fail(PBN_EINVAL, "copy_bytes < 0");
   if (copy_bytes > 0) {
     if (!d_copy_dst || !d_copy_src) return fail(PBN_EINVAL, "null copy buffer");
-    if ((copy_bytes & 15) || ((uintptr_t)d_copy_dst & 15u) || ((uintptr_t)d_copy_src & 15u))
+    if ((copy_bytes & 15) || !pbn::aligned(d_copy_dst, 16) || !pbn::aligned(d_copy_src, 16))
       return fail(PBN_EINVAL, "copy pointers and bytes must be 16-byte aligned");
     const char* d = static_cast<const char*>(d_copy_dst);
     const char* s = static_cast<const char*>(d_copy_src);

@@ -20,6 +20,7 @@
 #include <algorithm>
 
 #include "../../include/pbn_env.h"
+#include "host_check.h"
 #include "net_view.h"
 
 namespace {
@@ -119,7 +120,7 @@ __global__ void __launch_bounds__(kThreads) eval_reduce_kernel(const int32_t* __
 static_assert(kBins == kThreads, "eval_reduce_kernel zeroes and merges one bin per thread");
 static_assert(kMaxSteps + 2 <= kBins, "the histogram has max_steps + 2 bins");
 
-inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+using pbn::aligned;
 
 }  // namespace
 

@@ -42,6 +42,7 @@
 #include <algorithm>
 
 #include "../../include/pbn_env.h"
+#include "host_check.h"
 #include "net_view.h"
 #include "replay_draw.h"
 #include "wave_util.h"
@@ -57,7 +58,7 @@ constexpr int kMaxNT = 8;              // 16-column tiles of the bilinear layer'
 
 enum Seg { BIL_W, BIL_B, L2_W, L2_B, L3_W, L3_B, L4_W, L4_B, H1_W, H1_B, H2_W, H2_B, TOTAL };
 
-__host__ __device__ inline int64_t al16(int64_t x) { return (x + 15) & ~int64_t(15); }
+using pbn::al16;
 
 void make_layout(int N, int H, int64_t* off) {
   const int64_t A = N + 1;
@@ -1227,7 +1228,7 @@ int pbn_bdq_pack(const pbn_net* net, int32_t n_branches, const float* d_params, 
   if ((rc = pbn::check_device(net))) return rc;
   if ((rc = check_shape(v.n_nodes, n_branches))) return rc;
   if (!d_params || !d_Tq) return pbn::set_error(PBN_EINVAL, "null buffer");
-  if (((uintptr_t)d_params | (uintptr_t)d_Tq) & 15u) return pbn::set_error(PBN_EINVAL, "buffers: 16-byte aligned");
+  if (!pbn::aligned(d_params, 16) || !pbn::aligned(d_Tq, 16)) return pbn::set_error(PBN_EINVAL, "buffers: 16-byte aligned");
   const int N = v.n_nodes, H = n_branches + 1;
   LearnArgs a;
   memset(&a, 0, sizeof a);
@@ -1274,8 +1275,8 @@ int learn_launch(bool per, const pbn_net* net, int64_t batch, const int64_t* d_i
   if (per) {
     if (!d_weights) return pbn::set_error(PBN_EINVAL, "pbn_bdq_learn_per: null d_weights");
     if (!d_priority) return pbn::set_error(PBN_EINVAL, "pbn_bdq_learn_per: null d_priority");
-    if ((uintptr_t)d_weights & 3u) return pbn::set_error(PBN_EINVAL, "pbn_bdq_learn_per: d_weights must be 4-byte aligned");
-    if ((uintptr_t)d_priority & 3u) return pbn::set_error(PBN_EINVAL, "pbn_bdq_learn_per: d_priority must be 4-byte aligned");
+    if (!pbn::aligned(d_weights, 4)) return pbn::set_error(PBN_EINVAL, "pbn_bdq_learn_per: d_weights must be 4-byte aligned");
+    if (!pbn::aligned(d_priority, 4)) return pbn::set_error(PBN_EINVAL, "pbn_bdq_learn_per: d_priority must be 4-byte aligned");
     if ((rc = check_branches(n_branches))) return rc;
     if ((rc = check_batch(batch))) return rc;
   }
@@ -1295,7 +1296,7 @@ int learn_launch(bool per, const pbn_net* net, int64_t batch, const int64_t* d_i
   if (!d_Tq || !d_target_Tq) return pbn::set_error(PBN_EINVAL, "null network image");
   for (const void* p : {(const void*)d_params, (const void*)d_target_params, (const void*)d_adam_m,
                         (const void*)d_adam_v, (const void*)d_workspace, (const void*)d_Tq, (const void*)d_target_Tq})
-    if ((uintptr_t)p & 15u) return pbn::set_error(PBN_EINVAL, "parameter, table and workspace buffers: 16-byte aligned");
+    if (!pbn::aligned(p, 16)) return pbn::set_error(PBN_EINVAL, "parameter, table and workspace buffers: 16-byte aligned");
   const int H = n_branches + 1, A = N + 1;
   LearnArgs a;
   a.idx = d_idx;

@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "../../include/pbn_env.h"
+#include "host_check.h"
 #include "net_view.h"
 #include "philox.h"
 #include "wave_util.h"
@@ -804,8 +805,6 @@ __global__ void __launch_bounds__(64 * kWaves) qnet_tail_kernel(QnetArgs a) {
 #undef PBN_STAGE
 }
 
-bool al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 int qnet_check(const pbn_net* net, int64_t n_envs, const float* d_y, const float* d_w1, const float* d_b1,
                       const float* d_w2, const float* d_b2, const float* d_w3, const float* d_b3, const float* d_wh1,
                       const float* d_bh1, const float* d_wh2, const float* d_bh2, int32_t n_heads, int32_t n_actions) {
@@ -819,7 +818,8 @@ int qnet_check(const pbn_net* net, int64_t n_envs, const float* d_y, const float
     return pbn::set_error(PBN_EINVAL, "null buffer");
   // float4 weight-row and y loads: rows of 256 / 128 / 64 / 32 floats start 16-byte aligned
   // when the base is; the second head layer's rows are 64 floats
-  if (!al16(d_y) || !al16(d_w1) || !al16(d_w2) || !al16(d_w3) || !al16(d_wh1) || !al16(d_wh2))
+  if (!pbn::aligned(d_y, 16) || !pbn::aligned(d_w1, 16) || !pbn::aligned(d_w2, 16) || !pbn::aligned(d_w3, 16) ||
+      !pbn::aligned(d_wh1, 16) || !pbn::aligned(d_wh2, 16))
     return pbn::set_error(PBN_EINVAL, "y and weight buffers must be 16-byte aligned");
   return PBN_OK;
 }
@@ -844,16 +844,55 @@ int qnet_launch(const QnetArgs& a_in, void* stream) {
 }
 
 // the bilinear layer's inputs of the _from_state forms; on success fills a's BIL fields
-int bil_check(const pbn_net* net, const uint32_t* d_state, const uint8_t* d_target, const float* d_T,
+int bil_check(const pbn::NetView& v, const uint32_t* d_state, const uint8_t* d_target, const float* d_T,
               const float* d_b0, QnetArgs& a) {
+  if (!d_state || !d_target || !d_b0 || (v.n_attr > 0 && !d_T)) return pbn::set_error(PBN_EINVAL, "null buffer");
+  if (!pbn::aligned(d_b0, 16) || !pbn::aligned(d_T, 16))
+    return pbn::set_error(PBN_EINVAL, "d_b0 and d_T must be 16-byte aligned");
+  a.state = d_state; a.target = d_target; a.T = d_T; a.b0 = d_b0;
+  a.n_attr = v.n_attr;
+  return PBN_OK;
+}
+
+// The four entry points.  d_in is the tail's input: d_y, or with BIL the bilinear layer's bias d_b0
+// (d_state, d_target and d_T are BIL's).  n_k is n_heads, or with FLIP n_branches; seed .. env_offset,
+// epsilon, d_epsilon, d_flipmask and d_actions are FLIP's, d_heads the other forms'.
+template <bool FLIP, bool BIL>
+int qnet_impl(const pbn_net* net, uint64_t seed, uint64_t step, const uint64_t* d_step, uint64_t env_offset,
+              int64_t n_envs, const uint32_t* d_state, const uint8_t* d_target, const float* d_T, const float* d_in,
+              const float* d_w1, const float* d_b1, const float* d_w2, const float* d_b2, const float* d_w3,
+              const float* d_b3, const float* d_wh1, const float* d_bh1, const float* d_wh2, const float* d_bh2,
+              int32_t n_k, int32_t n_actions, float slope, float epsilon, const float* d_epsilon, float* d_heads,
+              uint32_t* d_flipmask, int32_t* d_actions, void* stream) {
   pbn::NetView v;
   int rc = pbn::net_view(net, &v);
   if (rc) return rc;
-  if (!d_state || !d_target || !d_b0 || (v.n_attr > 0 && !d_T)) return pbn::set_error(PBN_EINVAL, "null buffer");
-  if (!al16(d_b0) || !al16(d_T)) return pbn::set_error(PBN_EINVAL, "d_b0 and d_T must be 16-byte aligned");
-  a.state = d_state; a.target = d_target; a.T = d_T; a.b0 = d_b0;
-  a.n_attr = v.n_attr; a.n_nodes = v.n_nodes; a.W = v.W;
-  return PBN_OK;
+  if (FLIP && (n_k < 1 || n_k > kMaxHeads - 1)) return pbn::set_error(PBN_EINVAL, "n_branches must be 1..7");
+  const int32_t n_heads = FLIP ? n_k + 1 : n_k;
+  if ((rc = qnet_check(net, n_envs, d_in, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, d_wh1, d_bh1, d_wh2, d_bh2, n_heads,
+                       n_actions)))
+    return rc;
+  if constexpr (FLIP) {   // (checked for an empty batch too)
+    if (env_offset & 31) return pbn::set_error(PBN_EINVAL, "env_offset must be a multiple of 32");
+    if (n_actions != v.n_nodes + 1) return pbn::set_error(PBN_EINVAL, "n_actions must be n_nodes + 1");
+    if (const char* msg = pbn::explore_args_error(epsilon, d_step, d_epsilon)) return pbn::set_error(PBN_EINVAL, msg);
+  }
+  if (n_envs == 0) return PBN_OK;
+  QnetArgs a{};
+  if constexpr (BIL) {
+    if ((rc = bil_check(v, d_state, d_target, d_T, d_in, a))) return rc;
+  } else {
+    a.y = d_in;
+  }
+  if (FLIP ? !d_flipmask : !d_heads) return pbn::set_error(PBN_EINVAL, "null buffer");
+  a.w1 = d_w1; a.b1 = d_b1; a.w2 = d_w2; a.b2 = d_b2; a.w3 = d_w3; a.b3 = d_b3;
+  a.wh1 = d_wh1; a.bh1 = d_bh1; a.wh2 = d_wh2; a.bh2 = d_bh2; a.heads = d_heads;
+  a.n = n_envs; a.n_heads = n_heads; a.n_act = n_actions; a.slope = slope;
+  if (FLIP || BIL) { a.n_nodes = v.n_nodes; a.W = v.W; }
+  // explore iff EXPLORE word 0 < floor(epsilon * 2^32), as pbn_q_to_flipmask
+  a.seed = seed; a.step = step; a.env_offset = env_offset; a.eps_u = pbn::explore_threshold(epsilon);
+  a.d_step = d_step; a.d_eps = d_epsilon; a.flipmask = d_flipmask; a.actions = d_actions;
+  return qnet_launch<FLIP, BIL>(a, stream);
 }
 
 }  // namespace
@@ -871,15 +910,9 @@ int pbn_qnet_heads(const pbn_net* net, int64_t n_envs, const float* d_y, const f
                    const float* d_w2, const float* d_b2, const float* d_w3, const float* d_b3, const float* d_wh1,
                    const float* d_bh1, const float* d_wh2, const float* d_bh2, int32_t n_heads, int32_t n_actions,
                    float slope, float* d_heads, void* stream) {
-  int rc = qnet_check(net, n_envs, d_y, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, d_wh1, d_bh1, d_wh2, d_bh2, n_heads,
-                      n_actions);
-  if (rc || n_envs == 0) return rc;
-  if (!d_heads) return pbn::set_error(PBN_EINVAL, "null buffer");
-  QnetArgs a{};
-  a.y = d_y; a.w1 = d_w1; a.b1 = d_b1; a.w2 = d_w2; a.b2 = d_b2; a.w3 = d_w3; a.b3 = d_b3;
-  a.wh1 = d_wh1; a.bh1 = d_bh1; a.wh2 = d_wh2; a.bh2 = d_bh2; a.heads = d_heads;
-  a.n = n_envs; a.n_heads = n_heads; a.n_act = n_actions; a.slope = slope;
-  return qnet_launch<false, false>(a, stream);
+  return qnet_impl<false, false>(net, 0, 0, nullptr, 0, n_envs, nullptr, nullptr, nullptr, d_y, d_w1, d_b1, d_w2, d_b2,
+                                 d_w3, d_b3, d_wh1, d_bh1, d_wh2, d_bh2, n_heads, n_actions, slope, 0.f, nullptr,
+                                 d_heads, nullptr, nullptr, stream);
 }
 
 int pbn_qnet_flipmask(const pbn_net* net, uint64_t seed, uint64_t step, const uint64_t* d_step, uint64_t env_offset,
@@ -888,29 +921,9 @@ int pbn_qnet_flipmask(const pbn_net* net, uint64_t seed, uint64_t step, const ui
                       const float* d_wh2, const float* d_bh2, int32_t n_branches, int32_t n_actions, float slope,
                       float epsilon, const float* d_epsilon, uint32_t* d_flipmask, int32_t* d_actions,
                       void* stream) {
-  pbn::NetView v;
-  int rc = pbn::net_view(net, &v);
-  if (rc) return rc;
-  if (n_branches < 1 || n_branches > kMaxHeads - 1) return pbn::set_error(PBN_EINVAL, "n_branches must be 1..7");
-  if ((rc = qnet_check(net, n_envs, d_y, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, d_wh1, d_bh1, d_wh2, d_bh2,
-                       n_branches + 1, n_actions)))
-    return rc;
-  if (env_offset & 31) return pbn::set_error(PBN_EINVAL, "env_offset must be a multiple of 32");
-  if (n_actions != v.n_nodes + 1) return pbn::set_error(PBN_EINVAL, "n_actions must be n_nodes + 1");
-  if (!(epsilon >= 0.f && epsilon <= 1.f)) return pbn::set_error(PBN_EINVAL, "epsilon must be in [0, 1]");
-  if (d_step && ((uintptr_t)d_step & 7u) != 0) return pbn::set_error(PBN_EINVAL, "d_step must be 8-byte aligned");
-  if (d_epsilon && ((uintptr_t)d_epsilon & 3u) != 0) return pbn::set_error(PBN_EINVAL, "d_epsilon misaligned");
-  if (n_envs == 0) return PBN_OK;
-  if (!d_flipmask) return pbn::set_error(PBN_EINVAL, "null buffer");
-  QnetArgs a{};
-  a.y = d_y; a.w1 = d_w1; a.b1 = d_b1; a.w2 = d_w2; a.b2 = d_b2; a.w3 = d_w3; a.b3 = d_b3;
-  a.wh1 = d_wh1; a.bh1 = d_bh1; a.wh2 = d_wh2; a.bh2 = d_bh2;
-  a.n = n_envs; a.n_heads = n_branches + 1; a.n_act = n_actions; a.slope = slope;
-  // explore iff EXPLORE word 0 < floor(epsilon * 2^32), as pbn_q_to_flipmask
-  a.seed = seed; a.step = step; a.env_offset = env_offset; a.eps_u = (uint64_t)floor((double)epsilon * 4294967296.0);
-  a.d_step = d_step; a.d_eps = d_epsilon; a.flipmask = d_flipmask; a.actions = d_actions;
-  a.n_nodes = v.n_nodes; a.W = v.W;
-  return qnet_launch<true, false>(a, stream);
+  return qnet_impl<true, false>(net, seed, step, d_step, env_offset, n_envs, nullptr, nullptr, nullptr, d_y, d_w1,
+                                d_b1, d_w2, d_b2, d_w3, d_b3, d_wh1, d_bh1, d_wh2, d_bh2, n_branches, n_actions, slope,
+                                epsilon, d_epsilon, nullptr, d_flipmask, d_actions, stream);
 }
 
 int pbn_qnet_heads_from_state(const pbn_net* net, int64_t n_envs, const uint32_t* d_state, const uint8_t* d_target,
@@ -918,16 +931,9 @@ int pbn_qnet_heads_from_state(const pbn_net* net, int64_t n_envs, const uint32_t
                               const float* d_w2, const float* d_b2, const float* d_w3, const float* d_b3,
                               const float* d_wh1, const float* d_bh1, const float* d_wh2, const float* d_bh2,
                               int32_t n_heads, int32_t n_actions, float slope, float* d_heads, void* stream) {
-  QnetArgs a{};
-  int rc = qnet_check(net, n_envs, d_b0, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, d_wh1, d_bh1, d_wh2, d_bh2, n_heads,
-                      n_actions);
-  if (rc || n_envs == 0) return rc;
-  if ((rc = bil_check(net, d_state, d_target, d_T, d_b0, a))) return rc;
-  if (!d_heads) return pbn::set_error(PBN_EINVAL, "null buffer");
-  a.w1 = d_w1; a.b1 = d_b1; a.w2 = d_w2; a.b2 = d_b2; a.w3 = d_w3; a.b3 = d_b3;
-  a.wh1 = d_wh1; a.bh1 = d_bh1; a.wh2 = d_wh2; a.bh2 = d_bh2; a.heads = d_heads;
-  a.n = n_envs; a.n_heads = n_heads; a.n_act = n_actions; a.slope = slope;
-  return qnet_launch<false, true>(a, stream);
+  return qnet_impl<false, true>(net, 0, 0, nullptr, 0, n_envs, d_state, d_target, d_T, d_b0, d_w1, d_b1, d_w2, d_b2,
+                                d_w3, d_b3, d_wh1, d_bh1, d_wh2, d_bh2, n_heads, n_actions, slope, 0.f, nullptr,
+                                d_heads, nullptr, nullptr, stream);
 }
 
 int pbn_qnet_flipmask_from_state(const pbn_net* net, uint64_t seed, uint64_t step, const uint64_t* d_step,
@@ -938,28 +944,9 @@ int pbn_qnet_flipmask_from_state(const pbn_net* net, uint64_t seed, uint64_t ste
                                  const float* d_bh2, int32_t n_branches, int32_t n_actions, float slope,
                                  float epsilon, const float* d_epsilon, uint32_t* d_flipmask, int32_t* d_actions,
                                  void* stream) {
-  pbn::NetView v;
-  int rc = pbn::net_view(net, &v);
-  if (rc) return rc;
-  if (n_branches < 1 || n_branches > kMaxHeads - 1) return pbn::set_error(PBN_EINVAL, "n_branches must be 1..7");
-  if ((rc = qnet_check(net, n_envs, d_b0, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, d_wh1, d_bh1, d_wh2, d_bh2,
-                       n_branches + 1, n_actions)))
-    return rc;
-  if (env_offset & 31) return pbn::set_error(PBN_EINVAL, "env_offset must be a multiple of 32");
-  if (n_actions != v.n_nodes + 1) return pbn::set_error(PBN_EINVAL, "n_actions must be n_nodes + 1");
-  if (!(epsilon >= 0.f && epsilon <= 1.f)) return pbn::set_error(PBN_EINVAL, "epsilon must be in [0, 1]");
-  if (d_step && ((uintptr_t)d_step & 7u) != 0) return pbn::set_error(PBN_EINVAL, "d_step must be 8-byte aligned");
-  if (d_epsilon && ((uintptr_t)d_epsilon & 3u) != 0) return pbn::set_error(PBN_EINVAL, "d_epsilon misaligned");
-  if (n_envs == 0) return PBN_OK;
-  QnetArgs a{};
-  if ((rc = bil_check(net, d_state, d_target, d_T, d_b0, a))) return rc;
-  if (!d_flipmask) return pbn::set_error(PBN_EINVAL, "null buffer");
-  a.w1 = d_w1; a.b1 = d_b1; a.w2 = d_w2; a.b2 = d_b2; a.w3 = d_w3; a.b3 = d_b3;
-  a.wh1 = d_wh1; a.bh1 = d_bh1; a.wh2 = d_wh2; a.bh2 = d_bh2;
-  a.n = n_envs; a.n_heads = n_branches + 1; a.n_act = n_actions; a.slope = slope;
-  a.seed = seed; a.step = step; a.env_offset = env_offset; a.eps_u = (uint64_t)floor((double)epsilon * 4294967296.0);
-  a.d_step = d_step; a.d_eps = d_epsilon; a.flipmask = d_flipmask; a.actions = d_actions;
-  return qnet_launch<true, true>(a, stream);
+  return qnet_impl<true, true>(net, seed, step, d_step, env_offset, n_envs, d_state, d_target, d_T, d_b0, d_w1, d_b1,
+                               d_w2, d_b2, d_w3, d_b3, d_wh1, d_bh1, d_wh2, d_bh2, n_branches, n_actions, slope,
+                               epsilon, d_epsilon, nullptr, d_flipmask, d_actions, stream);
 }
 
 }  // extern "C"

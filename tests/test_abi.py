@@ -28,7 +28,90 @@ def lib():
 
 
 def test_header_declares_the_abi():
-    assert declared_functions() == sorted(_lib.EXPORTS)
+    """The looser regex above finds what _lib.declared()'s parser finds: it drops no declaration."""
+    assert declared_functions() == sorted(_lib.EXPORTS) == sorted(_lib.declared())
+
+
+SYNTHETIC = """
+/* a header in small: int pbn_in_a_comment(int x); */
+#define PBN_ABI_VERSION 7
+#define PBN_EINVAL (-22)
+typedef struct pbn_pair { int64_t a, b; const float* p; } pbn_pair;
+typedef struct pbn_net pbn_net;
+int pbn_make(const pbn_pair* pair, pbn_net** out);
+int pbn_many(pbn_net* net, uint64_t seed,   /* the key */
+             int64_t n_envs,                // any count
+             uint32_t mode, int32_t k, float slope, double beta,
+             const uint8_t* d_flags, void* stream);
+const char* pbn_why(void);
+int pbn_version(void);
+void pbn_quiet(int code);
+"""
+
+
+def test_parser_cases():
+    """Comments between parameters, (void), a const char* return, a pointer to a pointer."""
+    vp = ctypes.c_void_p
+    fns, version = _lib.parse_header(SYNTHETIC)
+    assert version == 7 and list(fns) == ["pbn_make", "pbn_many", "pbn_why", "pbn_version", "pbn_quiet"]
+    assert fns["pbn_make"].argtypes == (vp, vp) and fns["pbn_make"].params == ("pair", "out")
+    assert fns["pbn_make"].ctext == ("const pbn_pair* pair", "pbn_net** out")
+    many = fns["pbn_many"]
+    assert many.restype is ctypes.c_int
+    assert many.argtypes == (vp, ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint32, ctypes.c_int32, ctypes.c_float,
+                             ctypes.c_double, vp, vp)
+    assert many.params == ("net", "seed", "n_envs", "mode", "k", "slope", "beta", "d_flags", "stream")
+    assert fns["pbn_why"] == (ctypes.c_char_p, (), (), ())
+    assert fns["pbn_version"] == (ctypes.c_int, (), (), ())
+    assert fns["pbn_quiet"].restype is None and fns["pbn_quiet"].argtypes == (ctypes.c_int,)
+
+
+def test_parser_names_an_unknown_type():
+    with pytest.raises(_lib.PbnError, match=r"pbn_odd: parameter n .*'size_t"):
+        _lib.parse_header(SYNTHETIC + "int pbn_odd(pbn_net* net, size_t n);\n")
+    with pytest.raises(_lib.PbnError, match=r"pbn_odd: the return value"):
+        _lib.parse_header(SYNTHETIC + "size_t pbn_odd(void);\n")
+    with pytest.raises(_lib.PbnError, match="cannot parse"):      # not dropped: refused
+        _lib.parse_header(SYNTHETIC + "int (*pbn_callback)(int);\n")
+
+
+def test_every_declared_function_is_bound_as_declared(lib):
+    assert _lib.ABI_VERSION == 11 and len(_lib.declared()) == len(declared_functions())
+    for name, d in _lib.declared().items():
+        assert len(d.argtypes) == len(d.params) == len(d.ctext), name
+        assert d.restype is (ctypes.c_char_p if name == "pbn_last_error" else ctypes.c_int), name
+        fn = getattr(lib, name)
+        assert fn.restype is d.restype and tuple(fn.argtypes) == d.argtypes, name
+        assert all(t is ctypes.c_void_p for t, c in zip(d.argtypes, d.ctext) if "*" in c), name
+
+
+STALE = """
+const char* pbn_last_error(void) { return "stale"; }
+int pbn_abi_version(void) { return %d; }
+"""
+
+
+def _load_other(tmp_path, monkeypatch, version):
+    """_lib.load() of a tiny library that reports `version` and exports nothing else."""
+    src, so = tmp_path / f"v{version}.c", tmp_path / f"libv{version}.so"
+    src.write_text(STALE % version)
+    subprocess.run(["gcc", "-shared", "-fPIC", "-o", str(so), str(src)], check=True)
+    monkeypatch.setenv("PBN_LIB", str(so))
+    monkeypatch.setattr(_lib, "_lib", None)      # restored, with the real library, at teardown
+    return _lib.load()
+
+
+def test_load_refuses_a_stale_library(tmp_path, monkeypatch):
+    with pytest.raises(_lib.PbnError) as e:
+        _load_other(tmp_path, monkeypatch, 10)
+    assert "ABI version 10" in str(e.value) and "declares 11" in str(e.value) and "g.build()" in str(e.value)
+    assert _lib._lib is None
+
+
+def test_load_leaves_missing_symbols_unbound(tmp_path, monkeypatch):
+    L = _load_other(tmp_path, monkeypatch, 11)
+    assert L.pbn_abi_version() == 11 and L.pbn_last_error() == b"stale"
+    assert not hasattr(L, "pbn_step")
 
 
 def test_library_exports_every_symbol(lib):
@@ -45,19 +128,23 @@ def test_abi_version(lib):
 
 
 def test_descriptor_layout_matches_header(tmp_path):
-    """ctypes' pbn_net_desc == the C compiler's (sizeof and every offsetof, from the header)."""
-    import subprocess
-    fields = [f for f, _ in PbnNetDesc._fields_]
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "pbn_env.h"\nint main(void) {\n'
-                   '  printf("%zu\\n", sizeof(pbn_net_desc));\n' +
-                   "".join(f'  printf("%zu\\n", offsetof(pbn_net_desc, {f}));\n' for f in fields) + "  return 0;\n}\n")
-    exe = tmp_path / "layout"
+    """ctypes' mirrors of the three structs == the C compiler's (sizeof and every offsetof, from the
+    header); a field a mirror lacks would move sizeof, one it adds does not compile."""
     inc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include")
-    subprocess.run(["gcc", "-I", inc, "-o", str(exe), str(src)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert got[0] == ctypes.sizeof(PbnNetDesc)
-    assert got[1:] == [getattr(PbnNetDesc, f).offset for f in fields]
+    for c_name, mirror, n_fields in [("pbn_net_desc", PbnNetDesc, 20), ("pbn_ring_store", _lib.RingStore, 12),
+                                     ("pbn_frame_advance", _lib.FrameAdvance, 13)]:
+        fields = [f for f, _ in mirror._fields_]
+        assert len(fields) == n_fields, c_name
+        src = tmp_path / f"{c_name}.c"
+        src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "pbn_env.h"\nint main(void) {\n'
+                       f'  printf("%zu\\n", sizeof({c_name}));\n' +
+                       "".join(f'  printf("%zu\\n", offsetof({c_name}, {f}));\n' for f in fields) +
+                       "  return 0;\n}\n")
+        exe = tmp_path / c_name
+        subprocess.run(["gcc", "-I", inc, "-o", str(exe), str(src)], check=True)
+        got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
+        assert got[0] == ctypes.sizeof(mirror), c_name
+        assert got[1:] == [getattr(mirror, f).offset for f in fields], c_name
 
 
 def _create(lib, spec):

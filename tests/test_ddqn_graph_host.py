@@ -2,7 +2,6 @@
 anything touches the device), and pbn_ddqn_schedule's declaration, binding and argument checks."""
 import ctypes
 import os
-import re
 
 import pytest
 import torch
@@ -10,8 +9,6 @@ import torch
 from pbn_rl_amd import _lib
 from pbn_rl_amd.ddqn import DDQNLearner
 from tests.test_ddqn_host import StubEnv
-
-HEADER = os.path.join(os.path.dirname(__file__), "..", "include", "pbn_env.h")
 
 
 def _learner(**kw):
@@ -73,11 +70,9 @@ def test_eager_frames_are_unchanged_by_graphable():
 
 # ---- the export ------------------------------------------------------------------------------------
 def _declared_params(name):
-    """The parameter list of ``name``'s declaration in include/pbn_env.h."""
-    text = open(HEADER).read()
-    m = re.search(r"^int\s+" + name + r"\s*\(([^;]*?)\)\s*;", text, re.M | re.S)
-    assert m, f"{name} is not declared in pbn_env.h"
-    return [p.strip() for p in m.group(1).replace("\n", " ").split(",")]
+    """The parameter list of ``name``'s declaration in include/pbn_env.h, as the header spells it."""
+    assert name in _lib.declared(), f"{name} is not declared in pbn_env.h"
+    return list(_lib.declared()[name].ctext)
 
 
 @pytest.fixture(scope="module")

@@ -345,6 +345,15 @@ def test_qnet_flipmask_equals_heads_path(name, n, K, eps):
     assert torch.equal(env.flipmask, fm_ref)
 
 
+def rejects(fn, ok, changes):
+    """pbn_last_error() after `fn` has returned PBN_EINVAL for `ok` with `changes` ({index: value})."""
+    bad = list(ok)
+    for idx, val in changes.items():
+        bad[idx] = val
+    assert fn(*bad) == -22, changes
+    return _lib.load().pbn_last_error().decode()
+
+
 def test_qnet_flipmask_rejects_bad_arguments():
     spec = make_spec("pbn28")
     env = VectorPBNEnv(spec, 64, seed=1)
@@ -358,16 +367,23 @@ def test_qnet_flipmask_rejects_bad_arguments():
     h = env.net.handle
     ok = (h, 1, 0, None, 0, 64, *ptrs, 3, 29, 0.01, 0.0, None, fm, None, None)
     assert L.pbn_qnet_flipmask(*ok) == 0
-    bad = list(ok); bad[17] = 0                      # n_branches
-    assert L.pbn_qnet_flipmask(*bad) == -22
-    bad = list(ok); bad[18] = 30                     # n_actions != N + 1
-    assert L.pbn_qnet_flipmask(*bad) == -22
-    bad = list(ok); bad[20] = 1.5                    # epsilon
-    assert L.pbn_qnet_flipmask(*bad) == -22
-    bad = list(ok); bad[4] = 16                      # env_offset
-    assert L.pbn_qnet_flipmask(*bad) == -22
-    bad = list(ok); bad[22] = None                   # flipmask
-    assert L.pbn_qnet_flipmask(*bad) == -22
+    for changes, msg in [({17: 0}, "n_branches must be 1..7"),
+                         ({18: 30}, "n_actions must be n_nodes + 1"),
+                         ({20: 1.5}, "epsilon must be in [0, 1]"),
+                         ({4: 16}, "env_offset must be a multiple of 32"),
+                         ({22: None}, "null buffer"),                      # flipmask
+                         ({18: 30, 20: 1.5}, "n_actions must be n_nodes + 1"),          # two errors: the earlier check wins
+                         ({5: 40, 4: 16}, "n_envs must be a non-negative multiple of 32"),
+                         ({5: 0, 4: 16}, "env_offset must be a multiple of 32")]:       # checked for an empty batch too
+        assert rejects(L.pbn_qnet_flipmask, ok, changes) == msg, changes
+    bad = list(ok); bad[5] = 0; bad[22] = None       # an empty batch needs no buffers
+    assert L.pbn_qnet_flipmask(*bad) == 0
+    heads = torch.empty(4, 64, 29, device="cuda")
+    okh = (h, 64, *ptrs, 4, 29, 0.01, heads.data_ptr(), None)
+    assert L.pbn_qnet_heads(*okh) == 0
+    for changes, msg in [({14: 129, 2: ptrs[0] + 4}, "n_actions must be 1..128"),
+                         ({3: ptrs[1] + 4, 16: None}, "y and weight buffers must be 16-byte aligned")]:
+        assert rejects(L.pbn_qnet_heads, okh, changes) == msg, changes
     torch.cuda.synchronize()
 
 
@@ -439,19 +455,21 @@ def test_qnet_from_state_rejects_bad_arguments():
     h = env.net.handle
     ok = [h, 1, 0, None, 0, 64, st, tg, *ptrs, 3, 29, 0.01, 0.0, None, fm, None, None]
     assert L.pbn_qnet_flipmask_from_state(*ok) == 0
-    for idx, val in [(8, None),                       # T with attractors
-                     (8, ptrs[0] + 4),                # T misaligned (16-byte loads)
-                     (9, ptrs[1] + 4),                # b0 misaligned
-                     (6, None),                       # state
-                     (20, 0),                         # n_branches
-                     (21, 30),                        # n_actions != N + 1
-                     (5, 40)]:                        # n_envs not a multiple of 32
-        bad = list(ok)
-        bad[idx] = val
-        assert L.pbn_qnet_flipmask_from_state(*bad) == -22, idx
+    aligned16 = "d_b0 and d_T must be 16-byte aligned"
+    for changes, msg in [({8: None}, "null buffer"),                      # T with attractors
+                         ({8: ptrs[0] + 4}, aligned16),                   # T misaligned (16-byte loads)
+                         ({9: ptrs[1] + 4}, "y and weight buffers must be 16-byte aligned"),   # b0: the tail's input
+                         ({6: None}, "null buffer"),                      # state
+                         ({20: 0}, "n_branches must be 1..7"),
+                         ({21: 30}, "n_actions must be n_nodes + 1"),
+                         ({5: 40}, "n_envs must be a non-negative multiple of 32"),
+                         ({8: ptrs[0] + 4, 25: None}, aligned16),         # two errors: T before the null flipmask
+                         ({5: 0, 8: None, 4: 16}, "env_offset must be a multiple of 32")]:   # empty batch: still checked
+        assert rejects(L.pbn_qnet_flipmask_from_state, ok, changes) == msg, changes
     heads = torch.empty(4, 64, 29, device="cuda")
     okh = [h, 64, st, tg, *ptrs, 4, 29, 0.01, heads.data_ptr(), None]
     assert L.pbn_qnet_heads_from_state(*okh) == 0
-    bad = list(okh); bad[3] = None
-    assert L.pbn_qnet_heads_from_state(*bad) == -22
+    for changes, msg in [({3: None}, "null buffer"),                      # target
+                         ({4: ptrs[0] + 4, 19: None}, aligned16)]:        # two errors: T before the null heads
+        assert rejects(L.pbn_qnet_heads_from_state, okh, changes) == msg, changes
     torch.cuda.synchronize()

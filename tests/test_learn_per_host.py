@@ -1,6 +1,7 @@
 """Host side of the fused BDQ update on a prioritised batch (pbn_bdq_learn_per; no GPU): the entry
 is exported and declared, refuses bad arguments before it looks at the net or touches a device,
 and FusedBDQUpdate / BDQLearner refuse bad arguments by name."""
+import ctypes
 import os
 import re
 import subprocess
@@ -11,7 +12,6 @@ import torch
 from pbn_rl_amd import _lib
 from pbn_rl_amd.replay import BDQLearner, FusedBDQUpdate
 
-HEADER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "pbn_env.h")
 EINVAL = -22
 P = 0x10000     # a non-null, 16-byte aligned address: every call below must return before using it
 
@@ -33,10 +33,11 @@ def _learn_per(lib, B=32, K=3, w=P, prio=P):
 
 def test_entry_is_exported_and_declared(lib):
     assert hasattr(lib, "pbn_bdq_learn_per") and "pbn_bdq_learn_per" in _lib.EXPORTS
+    decl = _lib.declared()["pbn_bdq_learn_per"]
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True,
                          check=True).stdout
     assert re.search(r" T pbn_bdq_learn_per$", out, re.M)
-    assert re.search(r"^int\s+pbn_bdq_learn_per\s*\(", open(HEADER).read(), re.M)
+    assert decl.restype is ctypes.c_int and len(decl.params) == len(lib.pbn_bdq_learn_per.argtypes) == 34
     assert lib.pbn_abi_version() == 11
 
 

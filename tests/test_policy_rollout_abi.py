@@ -1,6 +1,7 @@
 """pbn_rollout_dqn in the C-ABI (no GPU needed): the symbol is exported under an unchanged ABI
 version, and a null net and the argument errors that need no net are rejected, each with its
 reason, before any device call."""
+import ctypes
 import os
 import re
 import subprocess
@@ -30,7 +31,9 @@ def test_rollout_dqn_is_exported_and_the_abi_version_stays(lib):
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True,
                          check=True).stdout
     assert "pbn_rollout_dqn" in set(re.findall(r" T (\w+)$", out, re.M))
-    assert hasattr(lib, "pbn_rollout_dqn") and lib.pbn_rollout_dqn.argtypes is not None
+    decl = _lib.declared()["pbn_rollout_dqn"]
+    assert hasattr(lib, "pbn_rollout_dqn") and tuple(lib.pbn_rollout_dqn.argtypes) == decl.argtypes
+    assert decl.restype is ctypes.c_int and len(decl.params) == 22
     assert lib.pbn_abi_version() == 11
 
 

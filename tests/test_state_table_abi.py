@@ -1,6 +1,7 @@
 """pbn_table_insert in the C-ABI (no GPU needed): the symbol is exported under an unchanged ABI
 version, and every argument error is rejected with its reason before any device call (all device
 pointers are null here), while an empty input is accepted."""
+import ctypes
 import os
 import re
 import subprocess
@@ -31,8 +32,9 @@ def test_table_insert_is_exported_and_the_abi_version_stays(lib):
     assert "pbn_table_insert" in set(re.findall(r" T (\w+)$", out, re.M))
     assert hasattr(lib, "pbn_table_insert") and lib.pbn_table_insert.argtypes is not None
     assert lib.pbn_abi_version() == 11
-    header = open(os.path.join(_lib.INCLUDE_DIR, "pbn_env.h")).read()
-    assert "int pbn_table_insert(" in header and "#define PBN_ABI_VERSION 11" in header
+    decl = _lib.declared()["pbn_table_insert"]
+    assert decl.restype is ctypes.c_int and tuple(lib.pbn_table_insert.argtypes) == decl.argtypes
+    assert len(decl.params) == 15 and _lib.ABI_VERSION == 11
 
 
 @pytest.mark.parametrize("over,msg", [
