@@ -1,5 +1,6 @@
 """Shapes at which the learned-agent kernels change path, shared by the edge sweeps
-(test_gpu_agent_edges.py, test_gpu_learn_edges.py, test_gpu_ddqn_edges.py).
+(test_gpu_agent_edges.py, test_gpu_learn_edges.py, test_gpu_ddqn_edges.py) and by the Adam-state
+tests (test_gpu_adam_state.py; the updates' shared inputs and float64 references: edge_updates.py).
 
 The bundled networks pin N to 7, 28, 33 or 70, so A = N + 1 to {8, 29, 34, 71} and the state to
 1-3 words.  The kernels are specialised on exactly these quantities; EDGE_N holds the last N

@@ -58,9 +58,9 @@ def _nets(N, arch, seed):
     return q.cuda(), tgt.cuda()
 
 
-def _ring(spec, cap, seed):
+def _ring(spec, cap, seed, device="cuda"):
     """A ring of random transitions (one action each; one target in ten missing) and its arrays."""
-    dev = torch.device("cuda")
+    dev = torch.device(device)
     R = DeviceReplay(cap, spec.words, 1, dev)
     rng = np.random.default_rng(seed)
     N, W = spec.n, spec.words
@@ -84,12 +84,12 @@ def _bits(words, N):
     return (w & 1).reshape(words.shape[1], -1)[:, :N].astype(np.float32)
 
 
-def _batch(spec, a, idx):
+def _batch(spec, a, idx, device="cuda"):
     """Rows idx of the ring's arrays as ddqn_update's batch, unpacked here (not by the library)."""
     first = np.zeros((256, spec.n), np.float32)
     for t, att in enumerate(spec.attractors):
         first[t] = att[0]
-    to = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()  # noqa: E731
+    to = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(device)  # noqa: E731
     return {"state": to(_bits(a["st"][:, idx], spec.n)), "target": to(first[a["tg"][idx]]),
             "next_state": to(_bits(a["nst"][:, idx], spec.n)), "action": to(a["act"][idx].astype(np.int64)),
             "reward": to(a["rew"][idx].reshape(-1, 1)), "done": to(a["done"][idx].astype(np.float32).reshape(-1, 1))}

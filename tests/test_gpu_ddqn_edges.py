@@ -18,15 +18,16 @@ import pytest
 import torch
 
 from pbn_rl_amd import _lib
-from pbn_rl_amd.ddqn import DQN, BatchedDDQN, FusedDDQNUpdate, ddqn_update
+from pbn_rl_amd.ddqn import BatchedDDQN, FusedDDQNUpdate, ddqn_update
 from pbn_rl_amd.vector_env import VectorPBNEnv
 from tests.edge_shapes import ENVS, FLOAT_BOUNDS, NO_TARGET, check_close, edge_spec, u32
-from tests.test_gpu_ddqn import RC, ZERO_AT, _batch, _ring
+from tests.edge_updates import batch64_of, ddqn_conditions, ddqn_inputs
+from tests.edge_updates import make_dqn_nets as make_nets
+from tests.test_gpu_ddqn import RC, ZERO_AT, _batch
 from tests.test_gpu_policy_rollout import run_pair, steps_are_the_oracles
 
 pytestmark = pytest.mark.gpu
 
-CAP = 1024
 # EDGE_N and 3, the archs spread over them: every arch at W = 1 (N <= 32) and at W = 4 (N >= 97)
 CASES = [(3, (1, 1)), (15, (16, 17)), (16, (17, 64)), (31, (64, 16)), (32, (16, 17)), (33, (17, 64)),
          (64, (64, 16)), (65, (1, 1)), (95, (16, 17)), (96, (17, 64)), (97, (64, 16)), (97, (1, 1)),
@@ -38,17 +39,6 @@ SEEDS = {}
 
 def batch_size(N):
     return 16 if N % 2 else 48
-
-
-def make_nets(N, arch, seed):
-    """The online network and a perturbed target, both built on the CPU generator."""
-    torch.manual_seed(seed)
-    q = DQN(N, N + 1, [arch])
-    tgt = copy.deepcopy(q)
-    with torch.no_grad():
-        for p in tgt.parameters():
-            p.add_(0.05 * torch.randn_like(p))
-    return q, tgt
 
 
 # ---- acting ---------------------------------------------------------------------------------------
@@ -104,14 +94,7 @@ def test_acting_launch_matches_the_module_and_the_explore_law(N, arch):
 # ---- the update against PyTorch in float64 --------------------------------------------------------
 def update_inputs(N, arch):
     """test_gpu_ddqn.py's _inputs on an edge spec, the weights drawn on the host."""
-    spec, B = edge_spec(N), batch_size(N)
-    R, a = _ring(spec, CAP, seed=SEEDS.get((N, arch), 100 + N))
-    rng = np.random.default_rng(B + N)
-    idx = rng.integers(0, CAP, size=B)
-    idx[3] = idx[7] = idx[1]                    # one ring row three times, each with its own weight
-    w = (rng.random(B) + 0.05).astype(np.float32)
-    w[ZERO_AT] = 0.0
-    return spec, B, R, a, idx, w
+    return ddqn_inputs(N, batch_size(N), SEEDS.get((N, arch), 100 + N))
 
 
 @pytest.mark.parametrize("clip", [False, True], ids=["noclip", "clip"])
@@ -126,16 +109,11 @@ def test_fused_update_matches_pytorch_in_float64(N, arch, clip):
     q32, tgt32 = copy.deepcopy(q), copy.deepcopy(tgt)
     lr, gamma = 1e-3, 0.95
     batch = _batch(spec, a, idx)
-    batch64 = {k: (v.double() if v.is_floating_point() else v) for k, v in batch.items()}
+    batch64 = batch64_of(batch)
     # the reference's input conditions: no argmax tie in Q(s'), |delta| on both sides of 1
-    with torch.no_grad():
-        qn = q64(batch64["next_state"], batch64["target"])
-        top2 = qn.topk(2, dim=1)[0]
-        assert float((top2[:, 0] - top2[:, 1]).min()) > 1e-4
-        y = batch64["reward"] + (1 - batch64["done"]) * gamma * tgt64(batch64["next_state"], batch64["target"]).gather(
-            1, qn.argmax(1, keepdim=True))
-        delta = (q64(batch64["state"], batch64["target"]).gather(1, batch64["action"]) - y).abs()
-        assert bool((delta < 1).any()) and bool((delta > 1).any())
+    gap, delta = ddqn_conditions(q64, tgt64, batch64, gamma)
+    assert gap > 1e-4
+    assert bool((delta < 1).any()) and bool((delta > 1).any())
     # the gradient norm of this batch decides what clips: half of it, or far above it
     probe = copy.deepcopy(q64)
     _, norm0 = ddqn_update(probe, tgt64, torch.optim.SGD(probe.parameters(), lr=0.0), batch64, gamma, 1e30,

@@ -22,10 +22,10 @@ from pbn_rl_amd.vector_env import VectorPBNEnv
 pytestmark = pytest.mark.gpu
 
 
-def _filled_replay(spec, K, cap, seed):
+def _filled_replay(spec, K, cap, seed, device="cuda"):
     """A ring of random transitions: random states, targets (one in ten without a target), actions
     0..N, rewards, done flags."""
-    dev = torch.device("cuda")
+    dev = torch.device(device)
     R = DeviceReplay(cap, spec.words, K, dev)
     rng = np.random.default_rng(seed)
     N, W = spec.n, spec.words

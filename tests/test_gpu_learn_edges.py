@@ -13,21 +13,18 @@ double-DQN argmax is then the same in float32 and float64)."""
 import copy
 import ctypes
 
-import numpy as np
 import pytest
 import torch
 
 from pbn_rl_amd import _lib
-from pbn_rl_amd.agent import BranchingQNetwork
 from pbn_rl_amd.replay import FusedBDQUpdate, bdq_update, fused_update_supported
 from pbn_rl_amd.vector_env import VectorPBNEnv
 from tests.edge_shapes import EDGE_N, edge_spec, u32
-from tests.test_gpu_learn import _check_image, _filled_replay
+from tests.edge_updates import batch_of, bdq_reference_update, bdq_ring, bdq_top2_gap, make_nets, pick_rows
+from tests.test_gpu_learn import _check_image
 
 pytestmark = pytest.mark.gpu
 
-CAP = 256
-ZERO_ROW, ONES_ROW = 0, 1
 SHAPES = ([(N, B, 3) for N in EDGE_N for B in (16, 48)]
           + [(33, 16, 1), (33, 48, 7), (95, 48, 1), (95, 16, 7)])
 # the ring / index seed of a shape is B + K (test_gpu_learn.py's); these shapes take another one,
@@ -35,64 +32,11 @@ SHAPES = ([(N, B, 3) for N in EDGE_N for B in (16, 48)]
 SEEDS = {(65, 48, 3): 1013, (96, 48, 3): 1000}
 
 
-def make_nets(N, K, seed):
-    """The online network and a perturbed target, both built on the CPU generator."""
-    torch.manual_seed(seed)
-    q = BranchingQNetwork((N, N), N + 1, K)
-    tgt = copy.deepcopy(q)
-    with torch.no_grad():
-        for p in tgt.parameters():
-            p.add_(0.01 * torch.randn_like(p))
-    return q, tgt
-
-
-def edge_rows(spec, R):
-    """One ring row whose state is all zeros and one whose state has all N bits set."""
-    N, W = spec.n, spec.words
-    ones = np.full(W, 0xFFFFFFFF, np.uint32)
-    if N % 32:
-        ones[W - 1] = np.uint32((1 << (N % 32)) - 1)
-    R.state[:, ZERO_ROW] = 0
-    R.state[:, ONES_ROW] = torch.from_numpy(ones.view(np.int32)).to(R.state.device)
-
-
-def pick_rows(R, B, seed):
-    """B ring rows: the two edge rows, one row without a target, then seeded draws."""
-    idx = np.random.default_rng(seed).integers(0, CAP, size=B)
-    idx[0], idx[1] = ZERO_ROW, ONES_ROW
-    none = np.flatnonzero(R.target.cpu().numpy() == 255)
-    idx[2] = none[none > ONES_ROW][0]
-    return idx
-
-
-def bits(words, N):
-    """(W, B) uint32 -> (B, N) float64"""
-    w = words.T[:, :, None] >> np.arange(32, dtype=np.uint32)[None, None, :]
-    return (w & 1).reshape(words.shape[1], -1)[:, :N].astype(np.float64)
-
-
-def batch_of(spec, R, idx, device, dtype):
-    """Rows idx of the ring as bdq_update's batch, unpacked here (not by the library)."""
-    N = spec.n
-    first = np.zeros((256, N))
-    for t, att in enumerate(spec.attractors):
-        first[t] = att[0]
-    it = torch.from_numpy(idx).to(R.state.device)
-    g = first[R.target[it].cpu().numpy()]
-    to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=dtype)  # noqa: E731
-    return {"obs": to(np.stack([bits(u32(R.state[:, it]), N), g])),
-            "next_obs": to(np.stack([bits(u32(R.next_state[:, it]), N), g])),
-            "actions": R.action[it].to(device=device, dtype=torch.int64).unsqueeze(-1),
-            "rewards": R.reward[it].to(device=device, dtype=dtype).reshape(-1, 1),
-            "masks": R.done[it].to(device=device, dtype=dtype).reshape(-1, 1)}
-
-
 def run_update(N, B, K):
     spec = edge_spec(N)
     seed = SEEDS.get((N, B, K), B + K)
     env = VectorPBNEnv(spec, 32)
-    R = _filled_replay(spec, K, CAP, seed=seed)
-    edge_rows(spec, R)
+    R = bdq_ring(spec, K, seed)
     idx = pick_rows(R, B, seed)
     st = u32(R.state[:, torch.from_numpy(idx).cuda()])
     assert not st[:, 0].any() and sum(bin(int(x)).count("1") for x in st[:, 1]) == N
@@ -103,13 +47,10 @@ def run_update(N, B, K):
     lr, gamma = 1e-3, 0.9
     # the float64 reference and its input condition
     b64 = batch_of(spec, R, idx, "cpu", torch.float64)
-    with torch.no_grad():
-        top2 = q64(b64["next_obs"]).topk(2, dim=2)[0]
-        gap = float((top2[..., 0] - top2[..., 1]).min())
+    gap = bdq_top2_gap(q64, b64)
     print(f"N={N} B={B} K={K}: smallest top-2 gap of Q(s') {gap:.3e}")
     assert gap > 1e-4, gap
-    opt64 = torch.optim.Adam(q64.parameters(), lr=lr)
-    loss_ref = float(bdq_update(q64, tgt64, opt64, b64, gamma))
+    loss_ref = bdq_reference_update(q64, tgt64, b64, lr, gamma)
     # the PyTorch fp32 update on the same batch (printed beside the kernel's errors)
     opt32 = torch.optim.Adam(q32.parameters(), lr=lr)
     loss32 = float(bdq_update(q32, tgt32, opt32, batch_of(spec, R, idx, "cuda", torch.float32), gamma))
