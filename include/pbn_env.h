@@ -838,6 +838,60 @@ int pbn_rollout_dqn(pbn_net* net, uint64_t seed, uint64_t step, uint64_t env_off
                     uint32_t* d_obs, uint32_t* d_final_state, float* d_reward, uint8_t* d_flags,
                     uint16_t* d_updates, void* stream);
 
+/*
+ * Episode statistics on the device (pbn_rl_amd/episode_stats.py EpisodeStats, csrc/pbn_episode.hip):
+ * what the reference logs on the host every frame -- RecordEpisodeStatistics' rollout/ep_rew_mean and
+ * rollout/ep_len_mean (ddqn_per/__init__.py:67,357-377), the BDQ loop's ep_len, ep_reward and
+ * missed[(state_attractor_id, target_attractor_id)] (bdq_model/__init__.py:179-236) -- kept by one
+ * call per frame that a captured frame can hold.  Additive exports (the ABI version is unchanged).
+ * All buffers are the caller's; both calls are asynchronous on `stream` and allocate and synchronise
+ * nothing.  n_alloc is a multiple of 32 and 0 < n_real <= n_alloc: envs i >= n_real are padding,
+ * neither read nor written.
+ *
+ * Per-env state, [n_alloc] each: d_ret float (return of the open episode, the plain float sum of its
+ * rewards in frame order), d_len uint32 (its steps), d_src uint8 (attractor id of its first state,
+ * PBN_NO_TARGET if no attractor holds it), d_tgt uint8 (the target at its start).
+ *
+ * Aggregates, all int64 and written by integer atomics only, so that they do not depend on the
+ * order of the adds; the caller zeroes them:
+ *   d_totals [8]       frames, episodes, successes (closed with PBN_FLAG_TERMINATED), missed (closed
+ *                      with PBN_FLAG_TRUNCATED and not terminated: the reference's `missed`), len_sum,
+ *                      ret_sum, last_reward_sum (the closing step's reward: the BDQ loop's ep_reward =
+ *                      reward), unpaired (closed episodes whose source or target is no attractor id)
+ *   d_pairs [A][A][4]  per (source, target): episodes, missed, len_sum, ret_sum (A = the net's
+ *                      attractors; null only when A == 0)
+ *   d_hist [256]       closed episodes by length; bin 255 holds every length >= 255
+ *   d_series [R][8]    a copy of d_totals every log_every frames (below)
+ * A float enters a sum once, at the close, as the int64 __double2ll_rn((double)x * 1048576.0), i.e. in
+ * units of 2^-20: ret_sum and last_reward_sum hold while |sum of the returns| < 2^43.
+ *
+ * pbn_episode_begin opens an episode for every env i < n_real from its current state and target
+ * (after a reset or a set_state): ret = 0, len = 0, tgt = d_target[i], src = the attractor that holds
+ * d_state[:, i] (the net's attractor hash, the one the step kernels probe; state words 1..4).
+ *
+ * pbn_episode_track is one frame's bookkeeping, after the step (and after a learner's ring store):
+ * d_state / d_target hold what the step left, the fresh start and the new target where it autoreset.
+ * Per env i < n_real: ret += d_reward[i], len += 1; if d_flags[i] & done_mask, the episode closes --
+ * into the totals and d_hist[min(len, 255)], into d_pairs[src][tgt] when both are attractor ids, else
+ * into `unpaired` -- and the next one opens from d_state[:, i] and d_target[i] as pbn_episode_begin
+ * opens it.  Without autoreset a finished env keeps producing done steps, each of which closes a
+ * one-step episode: the call is meant for autoreset envs.  Two launches: the envs, then one wave that
+ * increments `frames` and, when log_every > 0 and frames % log_every == 0, copies the eight totals
+ * into row (frames / log_every - 1) mod series_rows of d_series.  With log_every == 0 `frames` still
+ * advances and d_series may be null.
+ * Rejects: n_alloc not a positive multiple of 32, n_real outside 1..n_alloc, a done_mask that is zero
+ * or has bits outside PBN_FLAG_TERMINATED | PBN_FLAG_TRUNCATED, a null buffer, float / uint32
+ * buffers not 4-byte and int64 buffers not 8-byte aligned, log_every < 0, series_rows < 1 or a null
+ * d_series with log_every > 0, a null d_pairs on a net with attractors.
+ */
+int pbn_episode_begin(const pbn_net* net, int64_t n_alloc, int64_t n_real, const uint32_t* d_state,
+                      const uint8_t* d_target, float* d_ret, uint32_t* d_len, uint8_t* d_src, uint8_t* d_tgt,
+                      void* stream);
+int pbn_episode_track(const pbn_net* net, int64_t n_alloc, int64_t n_real, uint32_t done_mask, const float* d_reward,
+                      const uint8_t* d_flags, const uint32_t* d_state, const uint8_t* d_target, float* d_ret,
+                      uint32_t* d_len, uint8_t* d_src, uint8_t* d_tgt, int64_t* d_totals, int64_t* d_pairs,
+                      int64_t* d_hist, int64_t log_every, int64_t series_rows, int64_t* d_series, void* stream);
+
 const char* pbn_last_error(void);
 int pbn_abi_version(void);
 

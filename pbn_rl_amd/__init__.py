@@ -10,5 +10,6 @@ Public surface:
   ddqn.DQN / DDQNLearner             the reference's DDQN / DDQN-PER agent over the batched envs
   ssd.compute_ssd_hist               steady-state distribution (dense bins, or sparse=True: any width)
   state_table.StateTable             visited-state counts in a device hash table
+  episode_stats.EpisodeStats         episode returns, lengths and per-pair misses kept on the device
 """
 __version__ = "0.1.0"

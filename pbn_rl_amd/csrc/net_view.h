@@ -16,6 +16,11 @@ struct NetView {
   const int32_t* att_start;     // device [n_attr + 1]
   const uint32_t* att_states;   // device [n_states * W]
   const uint32_t* att_first;    // device [n_attr * W]: attractor t's first state (the BDQ target input)
+  // the attractor hash the step kernels probe (step_parts.h attractor_lookup), in device memory
+  const uint32_t* att_hash;     // device [1 << hash_bits][hash_stride(W)], 16-byte aligned
+  int hash_bits;                // 0: no attractors
+  int hash_probes;              // the longest probe sequence (>= 1 when attractors exist)
+  uint32_t hash_mult[4];        // the hash's multipliers, one per state word
 };
 
 // 0 on success, else a PBN_E* code with pbn_last_error() set

@@ -136,6 +136,11 @@ int net_view(const pbn_net* net, NetView* v) {
   v->att_start = net->base.att_start;
   v->att_states = net->base.att_states;
   v->att_first = net->att_first.as<uint32_t>();
+  // the image is cdf [cdf_len] | reward rows [4 (N + 1)] | hash | ..., as the step kernels carve it
+  v->att_hash = net->base.tab + net->base.cdf_len + 4 * (net->base.n_nodes + 1);
+  v->hash_bits = net->base.hash_bits;
+  v->hash_probes = net->base.hash_probes;
+  memcpy(v->hash_mult, net->base.hash_mult, sizeof v->hash_mult);
   return PBN_OK;
 }
 

@@ -14,12 +14,27 @@ from typing import Callable, Optional
 import torch
 
 from . import _lib
+from .episode_stats import EpisodeStats
 
 __all__ = ["FrameLearner"]
 
 
 class FrameLearner:
     """Reads the subclass's ``env``, ``replay``, ``prioritised``, ``epsilon`` and ``frame()``."""
+
+    stats: Optional[EpisodeStats] = None
+
+    def _init_stats(self, episode_stats: bool, stats_log_every: int) -> None:
+        """``episode_stats=True``: ``stats``, an EpisodeStats over the env's ``num_envs`` envs (those
+        whose (reward, done) ``frame()`` returns), opened on the env's current state and tracked
+        every frame; ``stats_log_every`` is its ``log_every``.  False: no launch is added."""
+        self.stats = EpisodeStats(self.env, log_every=stats_log_every) if episode_stats else None
+
+    def _track_stats(self) -> None:
+        """The frame's episode bookkeeping: after the step and the ring store, eager or captured
+        (``env.state`` and ``env.target`` then hold what the step left, under either step law)."""
+        if self.stats is not None:
+            self.stats.track()
 
     def _warm_up(self, ready: Callable[[], bool]) -> None:
         """Eager frames on a side stream (as graph capture requires) until ``ready()``."""
