@@ -129,6 +129,17 @@ __host__ __device__ __forceinline__ PhiloxPrefix philox_prefix(uint32_t c0, uint
   return pre;
 }
 
+// The prefix of the call that differs from `of`'s in counter word 2 alone: its own A, E and d3
+// beside `of`'s B and D, so a loop that pins both prefixes holds three more values, not five
+// (the env-draw wave's PERT call 0 beside its ENV call; sel_fast holds its CPN calls the same way)
+template <int R = kPhiloxRounds>
+__host__ __device__ __forceinline__ PhiloxPrefix philox_prefix_sibling(const PhiloxPrefix& of, uint32_t c0, uint32_t c2,
+                                                                        uint32_t c3, const uint32_t (&rk0)[R],
+                                                                        const uint32_t (&rk1)[R]) {
+  const PhiloxPrefix own = philox_prefix(c0, c2, c3, rk0, rk1);
+  return PhiloxPrefix{own.A, of.B, of.D, own.E, own.d3};
+}
+
 // philox_rk<R, XM>(c0, c1, c2, c3, rk0, rk1) from the prefix of (c0, c2, c3): one xor, one product
 // and one xor, one product and two xors, then rounds 4..R as they are
 template <int R = kPhiloxRounds, uint32_t XM = 0u>

@@ -307,6 +307,10 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
     uint32_t step_lo = (uint32_t)a.step;
     pbn::PhiloxPrefix pre = pbn::philox_prefix((uint32_t)ge, pbn::kStreamEnv << 28, ge_hi, rk0, rk1);
     asm volatile("" : "+v"(pre.A), "+v"(pre.B), "+v"(pre.D), "+v"(pre.E), "+v"(pre.d3));
+    // PERT call 0 of the lane (the rare fourth-flip tail) differs from its ENV call in counter word 2
+    // alone: the same B and D, and three more pinned values
+    pbn::PhiloxPrefix pre_pert = pbn::philox_prefix_sibling(pre, (uint32_t)ge, pbn::kStreamPert << 28, ge_hi, rk0, rk1);
+    asm volatile("" : "+v"(pre_pert.A), "+v"(pre_pert.E), "+v"(pre_pert.d3));
     auto env_call = [&]() { return pbn::philox_tail(pre, step_lo, rk0, rk1); };
     StepRows<uint32_t> fm_rows = rows_open(a.flipmask, n, (size_t)n_steps * plane);
     // one step (k < n_steps; `odd` = k & 1, known at compile time: the slot costs no select):
@@ -370,14 +374,24 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
 #pragma unroll
         for (int w = 0; w < W; ++w) rows_store(fm_rows, w, (size_t)w * n, le, valid, 8, m[w]);
         rows_advance(fm_rows, plane);
-        if (p2 < N - 1) {   // rare: a fourth flip is possible
-          // this step's low word: the running step is one ahead (no borrow: step_hi_fixed).  Another
-          // counter word 2 than the prefix's, so the whole call
+        PBN_PTAIL(k, p2 < N - 1);
+        // the rare fourth-flip tail (a lane in 400 at p = 0.01, N = 28: one iteration in six of a
+        // 64-lane wave): PERT call 0 from its pinned prefix, the fourth gap in line unless its word
+        // falls in the table's last bucket (no flip, three times in four), the further gaps out of
+        // line (gap_tail_split); then the two slot fields that hold the mask again.  (Deciding
+        // first and writing each field once was 2.5 % slower: the writes then trail the branch in
+        // every iteration.)  The state wave is waiting for this one by now: its ~30 dependent
+        // instructions issue at that wave's priority instead of behind the other two waves'
+        if (p2 < N - 1) {
+          PBN_ISA_ARM("gap_tail");   // (tools/isa_budget.py walks the iteration without it)
+          __builtin_amdgcn_s_setprio(kStatePrio);
+          // this step's low word: the running step is one ahead (no borrow: step_hi_fixed)
           const uint32_t step_lo_k = step_lo - 1u;
-          pbn::gap_tail<W>(
-              0u, 3, p2, N, E,
+          pbn::gap_tail_split<W>(
+              p2, N, pbn::philox_tail(pre_pert, step_lo_k, rk0, rk1),
               [&](int jj) { return pbn::philox_rk((uint32_t)ge, step_lo_k, pbn::gap_call_c2(0, jj), ge_hi, rk0, rk1); },
-              [&](uint32_t u) { return gap_lut(lut, a.gap_shift, a.gap_nb, u); }, gam);
+              [&](uint32_t u) { return gap_lut(lut, a.gap_shift, a.gap_nb, u); },
+              [&](uint32_t u) { return (u >> a.gap_shift) >= (uint32_t)a.gap_nb; }, gam);
           pert = false;
 #pragma unroll
           for (int w = 0; w < W; ++w) {
@@ -385,6 +399,7 @@ __global__ void __launch_bounds__(256) PBN_PIPE_ATTR pbn_rollout_pipe(StepArgs a
             slot[kGP + w * 64 + lane] = gam[w];
           }
           slot[kIN + lane] = rt | (pc << 8) | ((uint32_t)pert << 16);
+          __builtin_amdgcn_s_setprio(0);
         }
       }
       PBN_PSTAMP(k, 1);

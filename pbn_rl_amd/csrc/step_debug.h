@@ -43,6 +43,15 @@ namespace {
       if (a.stamps && (threadIdx.x & 63) == 0) a.stamps[(size_t)blockIdx.x * 32 + (idx_)] = t_; \
     }                                                                                         \
   } while (0)
+// pipelined rollout: how many lanes of the env-draw wave take the fourth-flip tail in the stamped
+// iteration, at column 19 of the block's row (tools/stamps.py splits the blocks by it)
+#define PBN_PTAIL(k, cond_)                                                                   \
+  do {                                                                                        \
+    if ((k) == 10) {                                                                          \
+      const unsigned long long n_ = __builtin_popcountll(__builtin_amdgcn_ballot_w64(cond_)); \
+      if (a.stamps && (threadIdx.x & 63) == 0) a.stamps[(size_t)blockIdx.x * 32 + 19] = n_;   \
+    }                                                                                         \
+  } while (0)
 // pipelined rollout, launch anatomy: the state wave's s_memrealtime (100 MHz, one clock for the
 // whole chip) at kernel entry, after the table image, at the loop start, after iterations 0 and
 // 1, after the loop and after its final stores have landed; row gridDim.x + block
@@ -66,6 +75,7 @@ namespace {
 #define PBN_STAMP(k) do {} while (0)
 #define PBN_PSTAMP(k, slot_) PBN_ISA_MARK("P" #slot_)
 #define PBN_PSTAMP_AT(k, idx_) PBN_ISA_MARK("A" #idx_)
+#define PBN_PTAIL(k, cond_) do {} while (0)
 #define PBN_RSTAMP(idx_) PBN_ISA_MARK("R" #idx_)
 // names the side of a runtime uniform branch it opens (tools/isa_budget.py --arms picks the live ones)
 #define PBN_ISA_ARM(name_)                                                                    \
@@ -85,6 +95,7 @@ namespace {
 #define PBN_STAMP(k) do {} while (0)
 #define PBN_PSTAMP(k, slot_) do {} while (0)
 #define PBN_PSTAMP_AT(k, idx_) do {} while (0)
+#define PBN_PTAIL(k, cond_) do {} while (0)
 #define PBN_RSTAMP(idx_) do {} while (0)
 #endif
 #ifndef PBN_ISA_LOOP

@@ -166,6 +166,21 @@ __host__ __device__ __forceinline__ void gap_tail(uint32_t k, int j, int pos, in
   }
 }
 
+// gap_tail(0, 3, p2, ...) for a loop that rarely gets there (callers test p2 < N - 1): the fourth
+// gap, word 0 of PERT call 0 (P0, which the caller has drawn), in line; gaps 4 and up, about 1e-5
+// per env-step at p = 0.01, as gap_tail's rolled loop behind a second unlikely branch.  past(u):
+// a cheap sufficient test that gap(u) > N (no position is left for it, whatever p2: no flip, and
+// the tail ends) which spares the gap's table read; the bucket table's sentinel bucket (gap_lut),
+// or never
+template <int W, typename Call, typename Gap, typename Past>
+__host__ __device__ __forceinline__ void gap_tail_split(int p2, int N, Word4 P0, Call call, Gap gap, Past past,
+                                                        uint32_t (&gam)[W]) {
+  if (past(P0.x)) return;
+  const int pos = p2 + gap(P0.x);
+  set_bit<W>(gam, pos, N);
+  if (__builtin_expect(pos < N - 1, 0)) gap_tail<W>(0u, 4, pos, N, P0, call, gap, gam);
+}
+
 // ---- the step's outcome from the attractor id of s' (-1: none), the env's target and t; horizon
 // 0: none; open: the settle law's last update left s' outside every attractor.  flags: the
 // PBN_FLAG_* byte; t saturates at 255 and is 0 after an autoreset.

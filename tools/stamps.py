@@ -107,6 +107,27 @@ def placement(full, it):
             "by_max_selection_waves_on_a_block_simd": by_worst}
 
 
+def tail_split(full, t, it):
+    """The blocks of the stamped iteration split by whether a lane of the env-draw wave took the
+    rare fourth-flip tail (column 19: the number of such lanes, step_debug.h PBN_PTAIL): per group
+    the iteration length, the state wave's barrier wait and the env-draw wave's work, in cycles."""
+    import numpy as np
+    lanes = full[:, 19]
+    out = {"tail_lanes_total": int(lanes.sum()), "tail_block_share": round(float((lanes > 0).mean()), 4)}
+    for name, sel in (("no_tail", lanes == 0), ("tail", lanes > 0)):
+        if not sel.any():
+            out[name] = {"blocks": 0}
+            continue
+        pct = lambda x, p: int(np.percentile(x[sel], p))
+        env_work, seg = t[:, 1, 1] - t[:, 1, 0], full[:, 5] - full[:, 17]
+        out[name] = {"blocks": int(sel.sum()),
+                     "iteration": {"median": pct(it, 50), "p90": pct(it, 90)},
+                     "state_barrier_wait": {"median": pct(t[:, 0, 2] - t[:, 0, 1], 50), "p90": pct(t[:, 0, 2] - t[:, 0, 1], 90)},
+                     "env_work": {"median": pct(env_work, 50), "p90": pct(env_work, 90), "max": pct(env_work, 100)},
+                     "env_masks_slot_writes_segment": {"median": pct(seg, 50), "p90": pct(seg, 90)}}
+    return out
+
+
 def anatomy(r, n_steps, hw=None):
     """Launch anatomy from the state waves' s_memrealtime stamps (100 MHz): entry, image in LDS,
     loop start, after iterations 0 and 1, loop end, final stores landed (columns 0..6)."""
@@ -216,6 +237,7 @@ def main():
         it = t[:, :, 2].max(axis=1) - t[:, :, 0].min(axis=1)
         rep["iteration_median"] = int(np.median(it))
         rep["critical_path"] = segments(full, it)
+        rep["tail_split"] = tail_split(full, t, it)
         rep["placement"] = placement(full, it)
         if args.rollout:
             rep["anatomy"] = anatomy(buf.view(-1, ROW)[waves:2 * waves, :7].cpu().numpy().astype(np.int64),
