@@ -892,6 +892,57 @@ int pbn_episode_track(const pbn_net* net, int64_t n_alloc, int64_t n_real, uint3
                       uint32_t* d_len, uint8_t* d_src, uint8_t* d_tgt, int64_t* d_totals, int64_t* d_pairs,
                       int64_t* d_hist, int64_t log_every, int64_t series_rows, int64_t* d_series, void* stream);
 
+/*
+ * Curriculum resets on the device (pbn_rl_amd/curriculum.py Curriculum, csrc/pbn_curriculum.hip; the
+ * law is csrc/curriculum_law.h's, DESIGN.md "Curriculum resets"): the reference's
+ * env.rework_probas(ep_len) (bdq_model/__init__.py:203) as two stages of a learning frame.  The step
+ * kernels keep the step law's uniform autoreset; pbn_curriculum_redraw then restarts the envs the
+ * step reset from a draw weighted by pbn_episode_track's pair statistics, and pbn_curriculum_refresh
+ * rebuilds the weights' prefix sums from them.  Additive exports (the ABI version is unchanged).  Both
+ * calls are asynchronous on `stream` and allocate and synchronise nothing.
+ *
+ * The table: one caller-owned device buffer of pbn_curriculum_table_bytes(A) bytes, 8-byte aligned,
+ * A = the net's attractors, 2..254.  With H = the spec's horizon (20 if it has none), E =
+ * d_pairs[s][t].episodes and L = d_pairs[s][t].len_sum:
+ *   w[s][t] = 0 if s == t, else min(floor(((H + L) << 8) / (1 + E)), 2^24 - 1)   (in uint64)
+ * and the buffer holds, in this order,
+ *   uint64 rowcdf[A]   rowcdf[s] = the sum of rows 0..s of w
+ *   uint32 cdf[A][A]   cdf[s][t] = w[s][0] + ... + w[s][t]; then padding to a multiple of 8 bytes
+ *   uint64 total       rowcdf[A - 1], below 2^40
+ *   uint64 refreshes   the rebuilds so far (the caller zeroes it)
+ * pbn_curriculum_table_bytes returns the size, or PBN_EINVAL for A outside 2..254.
+ *
+ * pbn_curriculum_redraw belongs after the step (and a learner's ring store) and before
+ * pbn_episode_track, so that the episode it opens is the redrawn one.  For every env i < n_real with
+ * d_flags[i] & PBN_FLAG_RESET and (x0, x1, x2, x3) = Philox call 0 of stream CURRICULUM (8) of env
+ * env_offset + i at the step's index k:
+ *   v = floor((x1:x0) total / 2^64), s = min{s : rowcdf[s] > v}, v' = v - rowcdf[s - 1] (rowcdf[-1] = 0),
+ *   t = min{t : cdf[s][t] > v'} (never s), row = att_start[s] + floor((x3:x2) size_s / 2^64)
+ * and d_state[:, i] becomes row `row` of the net's attractor-state table, d_target[i] = t, and
+ * d_target_copy[i] = t where d_target_copy is given (a captured settle-law frame carries the targets
+ * in a second buffer).  k is *d_step when d_step is given (read when the kernel runs: the index the
+ * captured frame's step used, before pbn_replay_advance), else `step` (an eager frame: the env's step
+ * index minus one after the step).  Every other env, and everything at i >= n_real, is neither read
+ * beyond its flag nor written.  d_state is [W][n_alloc] with W the net's state words, 1..4.
+ * Rejects, in this order: a null or foreign net, a net with fewer than two attractors, n_alloc not a
+ * positive multiple of 32 below 2^31, n_real outside 1..n_alloc, a null d_flags, d_state, d_target or
+ * d_table, d_state not 4-byte or d_table not 8-byte aligned, d_step not 8-byte aligned.
+ *
+ * pbn_curriculum_refresh belongs after pbn_episode_track (whose second launch counted the frame).
+ * One single-block launch: when refresh_every > 0 and d_totals[0] % refresh_every == 0, or when
+ * refresh_every == -1 ("now"), the whole table is rebuilt from d_pairs [A][A][4] in integers, the
+ * same for every schedule, and `refreshes` goes up by one; otherwise nothing is written.
+ * refresh_every == 0 never rebuilds and launches nothing.  horizon is H above.
+ * Rejects, in this order: n_attr outside 2..254, horizon outside 1..65535, refresh_every < -1, a null
+ * d_pairs or d_table, a null d_totals with refresh_every > 0, a buffer not 8-byte aligned.
+ */
+int pbn_curriculum_table_bytes(int32_t n_attr);
+int pbn_curriculum_redraw(const pbn_net* net, uint64_t seed, uint64_t step, const uint64_t* d_step, uint64_t env_offset,
+                          int64_t n_alloc, int64_t n_real, const uint8_t* d_flags, uint32_t* d_state, uint8_t* d_target,
+                          uint8_t* d_target_copy, const void* d_table, void* stream);
+int pbn_curriculum_refresh(const int64_t* d_totals, const int64_t* d_pairs, int32_t n_attr, int32_t horizon,
+                           int64_t refresh_every, void* d_table, void* stream);
+
 const char* pbn_last_error(void);
 int pbn_abi_version(void);
 

@@ -11,5 +11,6 @@ Public surface:
   ssd.compute_ssd_hist               steady-state distribution (dense bins, or sparse=True: any width)
   state_table.StateTable             visited-state counts in a device hash table
   episode_stats.EpisodeStats         episode returns, lengths and per-pair misses kept on the device
+  curriculum.Curriculum              restarts weighted by the per-pair statistics (rework_probas), on the device
 """
 __version__ = "0.1.0"

@@ -19,10 +19,12 @@ namespace pbn {
 // word k + 1 = branch k's random action, by multiply-high); SETTLE_SEL = 5 (per env: node i's
 // selection uniform of update k is 16-bit field i & 7 of call (k << 8) | (i >> 3)) and
 // SETTLE_ENV = 6 (per env): updates k >= 1 of a step under the settle law (settle_updates);
-// REPLAY = 7: the learner's replay rows (pbn_replay_advance: id = row of the batch, step = draw)
+// REPLAY = 7: the learner's replay rows (pbn_replay_advance: id = row of the batch, step = draw);
+// CURRICULUM = 8: the weighted restart of an env that the step reset (curriculum_law.h: call 0 of
+// the env at the step's index).  The stream field has four bits.
 enum : uint32_t {
   kStreamSel = 0, kStreamEnv = 1, kStreamPert = 2, kStreamReset = 3, kStreamExplore = 4,
-  kStreamSettleSel = 5, kStreamSettleEnv = 6, kStreamReplay = 7
+  kStreamSettleSel = 5, kStreamSettleEnv = 6, kStreamReplay = 7, kStreamCurriculum = 8
 };
 
 struct Word4 {

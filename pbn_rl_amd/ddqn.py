@@ -439,7 +439,12 @@ class DDQNLearner(FrameLearner):
 
     ``episode_stats=True`` keeps episode statistics on the device (``stats``, an EpisodeStats with
     ``log_every`` = ``stats_log_every``), tracked every frame, eager or captured: after ``run(k)``,
-    ``stats.series()`` holds the windows that elapsed inside the replays."""
+    ``stats.series()`` holds the windows that elapsed inside the replays.
+
+    ``curriculum=True`` (needs ``episode_stats=True``) is the reference's ``env.rework_probas``: the envs
+    a step reset restart from a (source, target) pair drawn by the per-pair statistics' weights
+    (``curriculum``, a Curriculum; the table is rebuilt every ``curriculum_refresh`` frames), inside
+    the frame, eager or captured."""
 
     def __init__(self, env, dqn: Optional[DQN] = None, *, net_arch=((50, 50),), total_frames: int,
                  capacity: int, batch_size: int = 64, target_update: int = 512, gamma: float = 0.95,
@@ -448,7 +453,8 @@ class DDQNLearner(FrameLearner):
                  train_frequency: int = 1, prioritised: bool = True, per_alpha: float = 0.6, per_beta: float = 0.4,
                  per_max_beta: float = 1.0, beta_fraction: float = 0.75, replay_constant: float = 1e-5,
                  fused: Optional[bool] = None, seed: int = 0, graphable: bool = False,
-                 episode_stats: bool = False, stats_log_every: int = 0):
+                 episode_stats: bool = False, stats_log_every: int = 0, curriculum: bool = False,
+                 curriculum_refresh: int = 1000):
         dev = torch.device(env.device)
         on_gpu = dev.type == "cuda"
         if prioritised and not on_gpu:
@@ -507,6 +513,7 @@ class DDQNLearner(FrameLearner):
         self.graphable = bool(graphable)
         self._graph: Optional[torch.cuda.CUDAGraph] = None
         self._init_stats(episode_stats, stats_log_every)
+        self._init_curriculum(curriculum, curriculum_refresh)
 
     def gather(self, idx: torch.Tensor) -> Dict[str, torch.Tensor]:
         """Rows ``idx`` of the ring as ``ddqn_update``'s batch (pbn_replay_batch when it takes the
@@ -559,7 +566,9 @@ class DDQNLearner(FrameLearner):
         _, reward, flags = env.step_flipmask(use_current=True)
         rp.store_at(self._pos_t, self._size_t, state, target, self.agent.actions.view(-1, 1), env.reward,
                     env.final_state, env.flags, done_mask=_lib.FLAG_TERMINATED)
+        self._redraw_resets()
         self._track_stats()
+        self._refresh_curriculum()
         rp.pos = (rp.pos + env.n_alloc) % rp.capacity
         rp.size = min(rp.size + env.n_alloc, rp.capacity)
         if f > self.learning_starts and f % self.train_frequency == 0 and rp.size >= max(self.batch_size, 2):
@@ -636,7 +645,9 @@ class DDQNLearner(FrameLearner):
         env, rp, fu = self.env, self.replay, self.fused
         self.agent.act_q(step_t=self._step_t, epsilon_t=self._eps32)
         self._step_and_store()
+        self._redraw_resets()
         self._track_stats()
+        self._refresh_curriculum()
         # the counters before the sample: it must see the fill level the store left, as the eager
         # frame's does
         self._advance_counters()

@@ -14,6 +14,7 @@ from typing import Callable, Optional
 import torch
 
 from . import _lib
+from .curriculum import Curriculum
 from .episode_stats import EpisodeStats
 
 __all__ = ["FrameLearner"]
@@ -23,12 +24,40 @@ class FrameLearner:
     """Reads the subclass's ``env``, ``replay``, ``prioritised``, ``epsilon`` and ``frame()``."""
 
     stats: Optional[EpisodeStats] = None
+    curriculum: Optional[Curriculum] = None
+    _tgt_prev: Optional[torch.Tensor] = None
 
     def _init_stats(self, episode_stats: bool, stats_log_every: int) -> None:
         """``episode_stats=True``: ``stats``, an EpisodeStats over the env's ``num_envs`` envs (those
         whose (reward, done) ``frame()`` returns), opened on the env's current state and tracked
         every frame; ``stats_log_every`` is its ``log_every``.  False: no launch is added."""
         self.stats = EpisodeStats(self.env, log_every=stats_log_every) if episode_stats else None
+
+    def _init_curriculum(self, curriculum: bool, curriculum_refresh: int) -> None:
+        """``curriculum=True`` (after ``_init_stats``; it needs ``episode_stats=True``): ``curriculum``,
+        a Curriculum over ``stats``, whose redraw and refresh run every frame around ``_track_stats``;
+        ``curriculum_refresh`` is its ``refresh_every``.  False: no launch is added."""
+        if curriculum and self.stats is None:
+            raise ValueError("curriculum=True needs episode_stats=True: the weights are the pair statistics'")
+        self.curriculum = Curriculum(self.env, self.stats, refresh_every=curriculum_refresh) if curriculum else None
+
+    def _redraw_resets(self) -> None:
+        """Between the ring store and ``_track_stats``: the envs the step reset restart from the
+        curriculum's draw, so the episode ``track`` opens, and ``pairs``, see the pair the env really
+        starts from.  Eager: the step ran at ``env.step_index - 1``; captured: at ``*_step_t``, which
+        advances later in the frame.  The settle law's captured frame carries the targets in
+        ``_tgt_prev``, which pbn_replay_store has already moved on: it is rewritten too."""
+        if self.curriculum is None:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            self.curriculum.redraw(step_t=self._step_t, target_copy=self._tgt_prev)
+        else:
+            self.curriculum.redraw()
+
+    def _refresh_curriculum(self) -> None:
+        """After ``_track_stats`` (which counted the frame): the table's rebuild, when due."""
+        if self.curriculum is not None:
+            self.curriculum.refresh()
 
     def _track_stats(self) -> None:
         """The frame's episode bookkeeping: after the step and the ring store, eager or captured

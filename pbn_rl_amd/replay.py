@@ -592,7 +592,12 @@ class BDQLearner(FrameLearner):
     it, the host mirroring beta as it mirrors epsilon.
 
     ``episode_stats=True`` keeps episode statistics on the device (``stats``, an EpisodeStats with
-    ``log_every`` = ``stats_log_every``), tracked every frame, eager or captured."""
+    ``log_every`` = ``stats_log_every``), tracked every frame, eager or captured.
+
+    ``curriculum=True`` (needs ``episode_stats=True``) is the reference's ``env.rework_probas(ep_len)``
+    (bdq_model/__init__.py:203): the envs a step reset restart from a (source, target) pair drawn by
+    the per-pair statistics' weights (``curriculum``, a Curriculum; the table is rebuilt every
+    ``curriculum_refresh`` frames), inside the frame, eager or captured."""
 
     def __init__(self, env: VectorPBNEnv, qnet: Optional[BranchingQNetwork] = None, *, capacity: int = 10 ** 4,
                  batch_size: int = 256, learning_rate: float = 1e-4, gamma: float = 0.999,
@@ -601,7 +606,7 @@ class BDQLearner(FrameLearner):
                  graphable: bool = False, blas: Optional[str] = "cublas", fused: Optional[bool] = None,
                  prioritised: bool = False, per_alpha: float = 0.6, per_beta: float = 0.4, per_max_beta: float = 1.0,
                  per_beta_steps: int = 10_000, replay_constant: float = 1e-5, episode_stats: bool = False,
-                 stats_log_every: int = 0):
+                 stats_log_every: int = 0, curriculum: bool = False, curriculum_refresh: int = 1000):
         if prioritised:   # (arguments that cannot work: refused before the env is looked at)
             if batch_size > 1024:
                 raise ValueError("prioritised replay samples at most 1024 rows per update")
@@ -669,6 +674,7 @@ class BDQLearner(FrameLearner):
         self._tw = None   # _target_weights()
         self._tw_key = None
         self._init_stats(episode_stats, stats_log_every)
+        self._init_curriculum(curriculum, curriculum_refresh)
 
     def _target_weights(self):
         """The target network's stacked head weights (BranchingQNetwork.head_weights), held in
@@ -702,7 +708,9 @@ class BDQLearner(FrameLearner):
         done_all = (env.flags & (_lib.FLAG_TERMINATED | _lib.FLAG_TRUNCATED)) != 0
         # all n_alloc envs are stored (the padding envs of a ragged batch are real envs too)
         self.replay.store(state, target, self.agent.actions, env.reward, env.final_state, done_all)
+        self._redraw_resets()
         self._track_stats()
+        self._refresh_curriculum()
         done = done_all[: env.num_envs]
         self.frames += 1
         if self.replay.size >= self.learning_starts:
@@ -805,7 +813,9 @@ class BDQLearner(FrameLearner):
         env = self.env
         self.agent.act_q(step_t=self._step_t, epsilon_t=self._eps32)
         self._step_and_store()
+        self._redraw_resets()
         self._track_stats()
+        self._refresh_curriculum()
         # then the counters: the step index, the ring position and fill level, epsilon (and, fused,
         # the next frame's rows) advance in the update's last launch or in pbn_replay_advance.  A
         # prioritised frame, fused or not, advances them before its updates: its sample must see the
