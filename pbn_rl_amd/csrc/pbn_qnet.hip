@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "../../include/pbn_env.h"
+#include "bdq_layout.h"
 #include "host_check.h"
 #include "net_view.h"
 #include "philox.h"
@@ -37,7 +38,7 @@ namespace {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kD0 = 256, kD1 = 128, kD2 = 64, kD3 = 32, kDH = 64;   // BranchingQNetwork widths
+using bdq::kD0, bdq::kD1, bdq::kD2, bdq::kD3, bdq::kDH;   // BranchingQNetwork widths
 constexpr int kMaxHeads = 8;                                         // value + up to 7 branches
 constexpr int kMaxActTiles = 4;                                      // A <= 128 (pbn70: 71), 32 per tile
 constexpr int kEnvs = 16;                                            // envs per wave

@@ -1,6 +1,6 @@
 // replay_draw.h -- the learning frame's counter advance and replay-row draw (library-internal),
 // shared by pbn_replay_advance's single-block kernel (pbn_agent.hip) and the fused update's
-// extra apply block (pbn_learn.hip, pbn_frame_advance).  One 256-thread block:
+// extra apply block (learn_apply.h, pbn_frame_advance).  One 256-thread block:
 //   *pos = (*pos + n_store) mod cap, *size = min(*size + n_store, cap)      (n_store > 0)
 //   *step += 1; *eps64 = max(eps_final, *eps64 - eps_step), *eps32 its fp32 copy
 //   idx[b] = mulhi64(x << 32 | y, draw_size) for the REPLAY Philox pair (x, y) of (seed, id = b,
@@ -12,6 +12,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "../../include/pbn_env.h"
 #include "philox.h"
 
 namespace pbn {
@@ -48,6 +49,16 @@ __device__ __forceinline__ void frame_advance_block(int64_t n_store, int64_t cap
     __syncthreads();
     if (threadIdx.x == 0) *counter = (int64_t)(c + 1);
   }
+}
+
+// What a fused update checks of the pbn_frame_advance that its extra block will run, on the host
+// (d_idx, batch: the update's own rows): the message of the first failure, or null.
+inline const char* frame_advance_error(const pbn_frame_advance& f, const int64_t* d_idx, int64_t batch) {
+  if (f.n_store < 0 || f.capacity < 1 || f.n_idx < 0 || !f.d_size || (f.n_store > 0 && !f.d_pos) ||
+      (f.n_idx > 0 && (!f.d_counter || !f.d_idx)))
+    return "pbn_frame_advance: n_store, n_idx >= 0, capacity >= 1, buffers";
+  if (f.d_idx == d_idx && f.n_idx < batch) return "pbn_frame_advance: d_idx draws fewer rows than the batch";
+  return nullptr;
 }
 
 }  // namespace pbn

@@ -1,5 +1,6 @@
 // wave_util.h -- the few wave-level helpers that the step kernels (step_parts.h), the DQN forward
-// (dqn_forward.h) and the BDQ kernels (pbn_qnet.hip, pbn_learn.hip) share: one definition each.
+// (dqn_forward.h) and the BDQ kernels (pbn_qnet.hip; learn_fwd.h, learn_bwd.h, learn_apply.h) share:
+// one definition each.
 #pragma once
 #include <hip/hip_runtime.h>
 

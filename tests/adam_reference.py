@@ -1,5 +1,5 @@
 """Adam past its first step: the float64 reference the fused updates' optimiser is held to
-(learn_apply_kernel, csrc/pbn_learn.hip; ddqn_adam_kernel, csrc/pbn_ddqn.hip), its bounds, and the
+(learn_apply_kernel, csrc/learn_apply.h; ddqn_adam_kernel, csrc/pbn_ddqn.hip), its bounds, and the
 seeded moments the tests start from (test_adam_reference_host.py, test_gpu_adam_state.py).
 
 The kernels take lr, beta1, beta2 and eps as ``float``, so their contract is torch.optim.Adam at
@@ -45,7 +45,7 @@ def adam_step64(p, m, v, t, g, lr, b1, b2, eps):
 
 
 def adam_step32_restated(p, m, v, t, g, lr, b1, b2, eps):
-    """The kernels' own expression (adam_apply, pbn_learn.hip; ddqn_adam_kernel), in their order, in
+    """The kernels' own expression (adam_apply, learn_apply.h; ddqn_adam_kernel), in their order, in
     fp32 numpy on the CPU.  Only ever used to show that a correct fp32 evaluation meets the bounds,
     never as what a kernel is compared with.  Returns (p', m', v') as fp32 tensors."""
     f = np.float32

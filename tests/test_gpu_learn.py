@@ -56,7 +56,7 @@ def _nets(N, K, seed):
 
 
 def _check_image(fused, q, N, K):
-    """The image's weight tiles (pbn_learn.hip make_image) restated from the module's weights:
+    """The image's weight tiles (csrc/bdq_layout.h make_image) restated from the module's weights:
     per dense layer (the three trunk layers, the stacked first head layers, the second head layers
     as (K + 1) x Apad rows, zero past each head's N + 1), tile (ot, kt) of 256 floats in two
     orders; fwd lane g*16 + r holds M[16ot + r][16kt + 4g + v], bwd M[16ot + 4g + v][16kt + r]."""

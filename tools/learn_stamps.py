@@ -5,7 +5,7 @@
 
 Runs eager BDQ training frames (bench.py --workload bdq-learn's learner) on the stamps build and
 reads the s_memtime clocks lane 0 of every wave stores in learn_fwd / learn_bwd / learn_apply
-(pbn_learn.hip PBN_LSTAMP), plus each wave's s_memrealtime at entry.  Prints one JSON object: per
+(csrc/learn_args.h PBN_LSTAMP), plus each wave's s_memrealtime at entry.  Prints one JSON object: per
 kernel, the median cycles from entry to every numbered point over the waves that reached it, and
 the spread of the blocks' entry times (100 MHz ticks).
 """
