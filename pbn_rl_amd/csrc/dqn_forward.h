@@ -10,6 +10,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "dqn_scalar.h"
 #include "host_check.h"
 #include "wave_util.h"
 
@@ -83,7 +84,8 @@ inline void make_dims(int N, int W, int n_attr, int h0, int h1, Dims* d) {
 
 // ---- the forward of 16 rows on one wave --------------------------------------------------------
 // Lane 16g + r works on row r.  sw: the row's state words (bits past N cleared), t: its target id.
-// y0[kb] / y1[kb] hold features 16 kb + 4g + v of row r after the ReLU (zero in the padding);
+// y0[kb] / y1[kb] hold features 16 kb + 4g + v of row r after the ReLU (F.relu: a NaN stays; exactly
+// zero in the padding, whatever the real features hold);
 // qf(at, q) receives Q[16 at + 4g + v][r] tile by tile, at ascending.
 // PRELOAD changes when the dense layers' operands are requested, and nothing of the arithmetic:
 // linears.0's tiles and bias before the table rows, the output layer's tile row at + 1 before the
@@ -144,10 +146,10 @@ __device__ __forceinline__ void forward16(const Dims& d, const float* __restrict
   }
 #pragma unroll
   for (int kb = 0; kb < kMaxHT; ++kb) {
-    y0[kb].x = fmaxf(y0[kb].x, 0.f);
-    y0[kb].y = fmaxf(y0[kb].y, 0.f);
-    y0[kb].z = fmaxf(y0[kb].z, 0.f);
-    y0[kb].w = fmaxf(y0[kb].w, 0.f);
+    y0[kb].x = pbn::relu(y0[kb].x);   // (a padded feature is 0 + zeros: it stays exactly 0)
+    y0[kb].y = pbn::relu(y0[kb].y);
+    y0[kb].z = pbn::relu(y0[kb].z);
+    y0[kb].w = pbn::relu(y0[kb].w);
   }
   // linears.0
   const float4* w1 = reinterpret_cast<const float4*>(img + d.iw1f) + lane;
@@ -179,8 +181,18 @@ __device__ __forceinline__ void forward16(const Dims& d, const float* __restrict
       float4 b;
       if constexpr (PRELOAD) b = bl[ot];
       else b = *reinterpret_cast<const float4*>(img + d.ib1 + 16 * ot + 4 * g);
-      y1[ot] = make_float4(fmaxf(acc[0] + b.x, 0.f), fmaxf(acc[1] + b.y, 0.f), fmaxf(acc[2] + b.z, 0.f),
-                           fmaxf(acc[3] + b.w, 0.f));
+      y1[ot] = make_float4(pbn::relu(acc[0] + b.x), pbn::relu(acc[1] + b.y), pbn::relu(acc[2] + b.z),
+                           pbn::relu(acc[3] + b.w));
+      // a padded row's sum is 0 * y0 + 0, which is NaN where a feature is infinite or NaN: the ReLU
+      // keeps a NaN, so the padding (the last tile's features 16 ot + 4g + v >= h1) is set to 0 by
+      // its index.  (wave-uniform branch: only a ragged last tile pays for it)
+      if (ot == d.H1T - 1 && (d.h1 & 15)) {
+        const int real = d.h1 - 16 * ot - 4 * g;   // this lane's real features of the tile
+        if (real < 1) y1[ot].x = 0.f;
+        if (real < 2) y1[ot].y = 0.f;
+        if (real < 3) y1[ot].z = 0.f;
+        if (real < 4) y1[ot].w = 0.f;
+      }
     }
   }
   // output

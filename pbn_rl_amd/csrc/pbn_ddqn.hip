@@ -259,9 +259,9 @@ __global__ void __launch_bounds__(192) ddqn_fb_kernel(LearnArgs a) {
   qsel += __shfl_xor(qsel, 32);
   const float qt = s_qt[s_ap[r] * 16 + r];
   const float y = a.rew[j] + ((1.f - (a.done[j] ? 1.f : 0.f)) * a.gamma) * qt;
-  const float delta = qsel - y, ad = fabsf(delta);
-  const float h = ad < 1.f ? 0.5f * delta * delta : ad - 0.5f;
-  float gq = fminf(fmaxf(delta, -1.f), 1.f) * (1.f / (float)B);   // d mean_b h_b / d q_b
+  const float delta = qsel - y;
+  const float h = pbn::huber(delta);
+  float gq = pbn::huber_grad(delta) * (1.f / (float)B);   // d mean_b h_b / d q_b (a NaN TD error: NaN)
   float l = h;
   if (a.wts) {
     const float wb = a.wts[b];
@@ -282,7 +282,10 @@ __global__ void __launch_bounds__(192) ddqn_fb_kernel(LearnArgs a) {
     }
     if (blockIdx.x == 0 && r == 0) a.step[0] += 1.f;   // Adam's step count, read by ddqn_adam
   }
-  // backward.  dQ is gq at (a_b, b) alone, so the output layer's transpose is one weight row
+  // backward.  dQ is gq at (a_b, b) alone, so the output layer's transpose is one weight row.
+  // The ReLU masks below are y > 0, which is false for a NaN feature, where torch's
+  // threshold_backward (x <= 0 ? 0 : g) passes g.  Nothing can tell them apart: a NaN feature makes
+  // the row's Q and so gq NaN, the norm NaN, and clip_coef then makes every gradient NaN.
   float4 dz1[kMaxHT], dz0[kMaxHT];
   const float* wo = a.P + d.off[OUT_W] + (int64_t)act * d.h1;
 #pragma unroll
@@ -457,8 +460,9 @@ __global__ void __launch_bounds__(kGradThreads) ddqn_adam_kernel(LearnArgs a) {
     __syncthreads();
   }
   const float total = sqrtf(red[0]);
-  // clip_grad_norm_: coef = max_norm / (total + 1e-6), at most 1; every gradient is multiplied
-  const float coef = fminf((1.f / (total + 1e-6f)) * a.max_norm, 1.f);
+  // clip_grad_norm_: coef = max_norm / (total + 1e-6), at most 1; every gradient is multiplied (by
+  // NaN when the norm is NaN)
+  const float coef = pbn::clip_coef(total, a.max_norm);
   if (blockIdx.x == 0 && tid == 0) {
     a.grad_norm[0] = total;
     float ls = 0.f;
@@ -479,12 +483,10 @@ __global__ void __launch_bounds__(kGradThreads) ddqn_adam_kernel(LearnArgs a) {
     }
     const float gv = G[e] * coef;
     if (a.grad) a.grad[e] = gv;
-    const float mm = a.b1 * a.m[e] + (1.f - a.b1) * gv;
-    const float vv = a.b2 * a.v[e] + (1.f - a.b2) * gv * gv;
-    a.m[e] = mm;
-    a.v[e] = vv;
-    const float denom = sqrtf(vv) / bc2s + a.eps;
-    a.P[e] = a.P[e] - (a.lr / bc1) * mm / denom;
+    const pbn::AdamElement n = pbn::adam_element(a.P[e], a.m[e], a.v[e], gv, a.lr, a.b1, a.b2, a.eps, bc1, bc2s);
+    a.m[e] = n.m;
+    a.v[e] = n.v;
+    a.P[e] = n.p;
   }
 }
 

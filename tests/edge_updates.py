@@ -10,9 +10,8 @@ import torch
 
 from pbn_rl_amd.agent import BranchingQNetwork
 from pbn_rl_amd.ddqn import DQN, ddqn_update
-from pbn_rl_amd.replay import bdq_update, soft_update
+from pbn_rl_amd.replay import DeviceReplay, bdq_update, soft_update
 from tests.edge_shapes import edge_spec, u32
-from tests.test_gpu_ddqn import ZERO_AT, _batch, _ring
 from tests.test_gpu_learn import _filled_replay
 
 # ---- BDQ (pbn_bdq_learn) ----------------------------------------------------------------------------
@@ -113,6 +112,44 @@ def bdq_trajectory_gaps(N, B, K, lr, ring_seed, row_seed, steps, soft_after=2, g
 
 # ---- DDQN (pbn_ddqn_learn) --------------------------------------------------------------------------
 DDQN_CAP = 1024
+ZERO_AT = 5                       # the batch position whose importance weight is 0
+
+
+def _ring(spec, cap, seed, device="cuda"):
+    """A ring of random transitions (one action each; one target in ten missing) and its arrays."""
+    dev = torch.device(device)
+    R = DeviceReplay(cap, spec.words, 1, dev)
+    rng = np.random.default_rng(seed)
+    N, W = spec.n, spec.words
+    st = rng.integers(0, 2 ** 32, size=(W, cap), dtype=np.uint64).astype(np.uint32)
+    nst = rng.integers(0, 2 ** 32, size=(W, cap), dtype=np.uint64).astype(np.uint32)
+    if N % 32:
+        st[W - 1] &= np.uint32((1 << (N % 32)) - 1)
+        nst[W - 1] &= np.uint32((1 << (N % 32)) - 1)
+    tg = rng.integers(0, len(spec.attractors), size=cap).astype(np.uint8)
+    tg[rng.random(cap) < 0.1] = 255
+    a = dict(st=st, nst=nst, tg=tg, act=rng.integers(0, N + 1, size=(cap, 1)).astype(np.int32),
+             rew=(1.5 * rng.standard_normal(cap)).astype(np.float32), done=(rng.random(cap) < 0.3).astype(np.uint8))
+    to = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+    R.store(to(st.view(np.int32)), to(tg), to(a["act"]), to(a["rew"]), to(nst.view(np.int32)), to(a["done"]))
+    return R, a
+
+
+def _bits(words, N):
+    """(W, B) uint32 -> (B, N) float32"""
+    w = words.T[:, :, None] >> np.arange(32, dtype=np.uint32)[None, None, :]
+    return (w & 1).reshape(words.shape[1], -1)[:, :N].astype(np.float32)
+
+
+def _batch(spec, a, idx, device="cuda"):
+    """Rows idx of the ring's arrays as ddqn_update's batch, unpacked here (not by the library)."""
+    first = np.zeros((256, spec.n), np.float32)
+    for t, att in enumerate(spec.attractors):
+        first[t] = att[0]
+    to = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(device)  # noqa: E731
+    return {"state": to(_bits(a["st"][:, idx], spec.n)), "target": to(first[a["tg"][idx]]),
+            "next_state": to(_bits(a["nst"][:, idx], spec.n)), "action": to(a["act"][idx].astype(np.int64)),
+            "reward": to(a["rew"][idx].reshape(-1, 1)), "done": to(a["done"][idx].astype(np.float32).reshape(-1, 1))}
 
 
 def make_dqn_nets(N, arch, seed):

@@ -23,6 +23,7 @@ from pbn_rl_amd.network import load_network
 from pbn_rl_amd.replay import DeviceReplay
 from pbn_rl_amd.spec import EnvSpec
 from pbn_rl_amd.vector_env import VectorPBNEnv
+from tests.edge_updates import ZERO_AT, _batch, _ring
 from tests.golden_parts import load_parts
 
 pytestmark = pytest.mark.gpu
@@ -34,7 +35,6 @@ N_ENVS, CAP = 96, 1024
 SHAPES = [("pbn7", [(8, 8)], 16), ("pbn28", [(50, 50)], 64), ("bb33", [(50, 50)], 32), ("pbn70", [(64, 64)], 16),
           ("pbn7", [(20, 40)], 16)]
 IDS = ["pbn7-8x8", "pbn28-50x50", "bb33-50x50", "pbn70-64x64", "pbn7-20x40"]
-ZERO_AT = 5
 _SPECS = {}
 
 
@@ -56,43 +56,6 @@ def _nets(N, arch, seed):
         for p in tgt.parameters():
             p.add_(0.05 * torch.randn_like(p))
     return q.cuda(), tgt.cuda()
-
-
-def _ring(spec, cap, seed, device="cuda"):
-    """A ring of random transitions (one action each; one target in ten missing) and its arrays."""
-    dev = torch.device(device)
-    R = DeviceReplay(cap, spec.words, 1, dev)
-    rng = np.random.default_rng(seed)
-    N, W = spec.n, spec.words
-    st = rng.integers(0, 2 ** 32, size=(W, cap), dtype=np.uint64).astype(np.uint32)
-    nst = rng.integers(0, 2 ** 32, size=(W, cap), dtype=np.uint64).astype(np.uint32)
-    if N % 32:
-        st[W - 1] &= np.uint32((1 << (N % 32)) - 1)
-        nst[W - 1] &= np.uint32((1 << (N % 32)) - 1)
-    tg = rng.integers(0, len(spec.attractors), size=cap).astype(np.uint8)
-    tg[rng.random(cap) < 0.1] = 255
-    a = dict(st=st, nst=nst, tg=tg, act=rng.integers(0, N + 1, size=(cap, 1)).astype(np.int32),
-             rew=(1.5 * rng.standard_normal(cap)).astype(np.float32), done=(rng.random(cap) < 0.3).astype(np.uint8))
-    to = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
-    R.store(to(st.view(np.int32)), to(tg), to(a["act"]), to(a["rew"]), to(nst.view(np.int32)), to(a["done"]))
-    return R, a
-
-
-def _bits(words, N):
-    """(W, B) uint32 -> (B, N) float32"""
-    w = words.T[:, :, None] >> np.arange(32, dtype=np.uint32)[None, None, :]
-    return (w & 1).reshape(words.shape[1], -1)[:, :N].astype(np.float32)
-
-
-def _batch(spec, a, idx, device="cuda"):
-    """Rows idx of the ring's arrays as ddqn_update's batch, unpacked here (not by the library)."""
-    first = np.zeros((256, spec.n), np.float32)
-    for t, att in enumerate(spec.attractors):
-        first[t] = att[0]
-    to = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(device)  # noqa: E731
-    return {"state": to(_bits(a["st"][:, idx], spec.n)), "target": to(first[a["tg"][idx]]),
-            "next_state": to(_bits(a["nst"][:, idx], spec.n)), "action": to(a["act"][idx].astype(np.int64)),
-            "reward": to(a["rew"][idx].reshape(-1, 1)), "done": to(a["done"][idx].astype(np.float32).reshape(-1, 1))}
 
 
 def _inputs(net, B):

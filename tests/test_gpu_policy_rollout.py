@@ -69,9 +69,10 @@ def twin_steps(agent, eps, n_steps):
     return {k: torch.stack(v) for k, v in rec.items()}
 
 
-def run_pair(spec, arch, n, check_updates=False):
-    """Fused launches against the twin for epsilon 0, 0.3 and 1; returns nothing, asserts."""
-    q = make_dqn(spec.n, arch)
+def run_pair(spec, arch, n, check_updates=False, q=None):
+    """Fused launches against the twin for epsilon 0, 0.3 and 1; returns nothing, asserts.  ``q``: the
+    network on the device (default: make_dqn's)."""
+    q = make_dqn(spec.n, arch) if q is None else q
     actions = {}
     for eps in (0.0, 0.3, 1.0):
         env, twin_env = make_env(spec, n), make_env(spec, n)
