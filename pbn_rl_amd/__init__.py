@@ -12,5 +12,6 @@ Public surface:
   state_table.StateTable             visited-state counts in a device hash table
   episode_stats.EpisodeStats         episode returns, lengths and per-pair misses kept on the device
   curriculum.Curriculum              restarts weighted by the per-pair statistics (rework_probas), on the device
+  checkpoint / learner.save, load    a training run written out and resumed bit-equal (tools/train.py)
 """
 __version__ = "0.1.0"

@@ -112,6 +112,13 @@ class Curriculum:
                 st.totals_t.data_ptr(), st.pairs_t.data_ptr(), self.n_attractors, self.horizon,
                 -1 if force else self.refresh_every, self.table_t.data_ptr(), v._stream()), "pbn_curriculum_refresh")
 
+    # ------------------------------------------------------------ checkpoints
+    def state_dict(self) -> dict:
+        return {"table_t": self.table_t.detach().to("cpu", copy=True)}
+
+    def load_state_dict(self, sd: dict) -> None:
+        self.table_t.copy_(sd["table_t"])
+
     # ------------------------------------------------------------ reading (each synchronises)
     def table(self) -> dict:
         """``rowcdf`` uint64 [A], ``cdf`` uint32 [A][A], ``total`` and ``refreshes`` (ints)."""

@@ -354,6 +354,8 @@ class FusedDDQNUpdate(FusedUpdate):
                          eps=eps, keep_grad=keep_grad)
         self.grad_norm = torch.zeros(1, dtype=torch.float32, device=self.q_flat.device)
 
+    _STATE_TENSORS = FusedUpdate._STATE_TENSORS + ("grad_norm",)
+
     def _sizes(self):
         L = _lib.load()
         nimg, nbytes = ctypes.c_int64(), ctypes.c_int64()
@@ -472,6 +474,7 @@ class DDQNLearner(FrameLearner):
         use_fused = can_fuse if fused is None else bool(fused)
         self.gen = torch.Generator(device=dev)
         self.gen.manual_seed(seed)
+        self.seed = int(seed)
         self.agent = BatchedDDQN(env, q, kernel=use_fused, generator=self.gen)
         self.q = self.agent.q.train()
         self.target = DQN(N, N + 1, self.q.net_arch).to(dev)
@@ -627,8 +630,8 @@ class DDQNLearner(FrameLearner):
         if self._graph is not None:
             raise ValueError("the frame is already captured")
         env, rp, dev = self.env, self.replay, torch.device(self.env.device)
-        self._warm_up(lambda: (self.frames > self.learning_starts and rp.size >= max(self.batch_size, 2)
-                               and self.updates >= min_updates))
+        # (a loaded checkpoint that already learns every frame: no eager frame runs)
+        self._warm_up(lambda: self._learns(self.frames, rp.size) and self.updates >= min_updates)
         self._capture_counters(self.min_epsilon, self.epsilon_decrement, 0)
         self._step_base = env.step_index - self.frames      # *step - base = the frames done
         rp.beta_t.fill_(self.beta)            # the next frame's beta; the schedule launch moves it from here on
@@ -660,6 +663,43 @@ class DDQNLearner(FrameLearner):
                 rp.beta_t.data_ptr(), float(self.beta_increment), self._step_t.data_ptr(), self._step_base,
                 self.target_update, fu.t_flat.data_ptr(), fu.q_flat.data_ptr(), fu.q_flat.numel(),
                 fu.t_image.data_ptr(), fu.q_image.data_ptr(), fu.q_image.numel(), env._stream()), "pbn_ddqn_schedule")
+
+    # ---- checkpoints (learner.py, checkpoint.py) ---------------------------------------------
+    agent_kind = "ddqn"
+
+    def _own_state(self) -> dict:
+        return {"frames": int(self.frames), "updates": int(self.updates), "epsilon": self.epsilon, "beta": self.beta,
+                "last_beta": self.last_beta, "syncs": [int(f) for f in self.syncs]}
+
+    def _learns(self, frames: int, size: int) -> bool:
+        """Whether every frame from ``frames`` on takes an update (what a captured frame does)."""
+        return frames > self.learning_starts and size >= max(self.batch_size, 2)
+
+    def _check_loadable_captured(self, host: dict) -> None:
+        """Into a captured learner: the checkpoint's frames must all learn from here on, and its
+        step index must count from the base the captured schedule launch holds."""
+        if not self._learns(int(host["learner.frames"]), int(host["replay.size"])):
+            raise ValueError("the checkpoint was saved before every frame learns (frames <= learning_starts, or "
+                             "fewer than batch_size rows): a captured frame always updates; load into a learner "
+                             "that is not captured yet")
+        base = int(host["env.step_index"]) - int(host["learner.frames"])
+        if base != self._step_base:
+            raise ValueError(f"checkpoint mismatch: env.step_index - frames (file {base}, captured frame "
+                             f"{self._step_base}): the captured target-copy schedule counts frames from it; load "
+                             "into a fresh learner and capture() after the load")
+
+    def _load_own_state(self, own: dict) -> None:
+        self.frames, self.updates = int(own["frames"]), int(own["updates"])
+        self.epsilon, self.beta, self.last_beta = own["epsilon"], own["beta"], own["last_beta"]
+        self.syncs[:] = [int(f) for f in own["syncs"]]
+        if self.prioritised:
+            # beta_t across the frame boundary: an eager frame leaves its own beta there, a captured
+            # one the next frame's (its schedule launch has moved it on)
+            rp = self.replay
+            if self._graph is not None:
+                rp.beta_t.fill_(self.beta)
+            else:
+                rp.beta_t.fill_(self.last_beta if self.last_beta is not None else rp.beta)
 
     def _mirror(self, k: int) -> None:
         """The host's copies after ``k`` replays: the eager frame's own arithmetic, ``k`` times."""

@@ -110,6 +110,26 @@ class EpisodeStats:
         self._mark()
         self.begin()
 
+    # ------------------------------------------------------------ checkpoints
+    _STATE_TENSORS = ("ret", "len", "src", "tgt", "totals_t", "pairs_t", "hist_t", "series_t")
+
+    def state_dict(self) -> dict:
+        """CPU copies of the per-env episode state and of the aggregates, and the baseline
+        ``window()`` differences against (``last_totals`` in TOTALS' order, ``last_missed``)."""
+        out = {k: getattr(self, k).detach().to("cpu", copy=True) for k in self._STATE_TENSORS
+               if getattr(self, k) is not None}
+        out["last_totals"] = [int(self._last_totals[k]) for k in TOTALS]
+        out["last_missed"] = torch.from_numpy(np.array(self._last_missed, dtype=np.int64))
+        return out
+
+    def load_state_dict(self, sd: dict) -> None:
+        """In place; ``window()`` then reports what happens after the checkpoint's last ``window()``."""
+        for k in self._STATE_TENSORS:
+            if getattr(self, k) is not None:
+                getattr(self, k).copy_(sd[k])
+        self._last_totals = dict(zip(TOTALS, (int(x) for x in sd["last_totals"])))
+        self._last_missed = np.array(sd["last_missed"].numpy(), dtype=np.int64)
+
     # ------------------------------------------------------------ reading (each synchronises)
     def _raw_totals(self) -> Dict[str, int]:
         return dict(zip(TOTALS, (int(x) for x in self.totals_t.cpu().tolist())))

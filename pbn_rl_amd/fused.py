@@ -101,6 +101,23 @@ class FusedUpdate:
         bump(self._tp)
         self._tv = _versions(self._tp)
 
+    # the buffers a checkpoint holds (FusedDDQNUpdate adds grad_norm).  The images and the workspace
+    # are derived: pack() reproduces bit for bit the images an update leaves
+    _STATE_TENSORS = ("q_flat", "t_flat", "m", "v", "step", "loss")
+
+    def state_dict(self) -> dict:
+        return {k: getattr(self, k).detach().to("cpu", copy=True) for k in self._STATE_TENSORS}
+
+    def load_state_dict(self, sd: dict) -> None:
+        """In place into the flat buffers (the nn.Parameters are views of them); then both images are
+        rebuilt and both networks marked as changed."""
+        with torch.no_grad():
+            for k in self._STATE_TENSORS:
+                getattr(self, k).copy_(sd[k])
+        self.pack("both")
+        self.mark_updated()
+        self.mark_target_updated()
+
     def _check_idx(self, idx: torch.Tensor) -> None:
         if idx.shape != (self.B,) or idx.dtype != torch.int64:
             raise ValueError(f"idx must be {self.B} int64 ring indices")

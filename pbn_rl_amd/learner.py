@@ -13,7 +13,7 @@ from typing import Callable, Optional
 
 import torch
 
-from . import _lib
+from . import _lib, checkpoint
 from .curriculum import Curriculum
 from .episode_stats import EpisodeStats
 
@@ -127,6 +127,127 @@ class FrameLearner:
         by one frame, in one launch."""
         self.replay.advance(self.env.n_alloc, self._pos_t, self._size_t, self._step_t, self._eps64, self._eps32,
                             float(self._eps_floor), float(self._eps_step), self._advance_seed)
+
+    # ---- checkpoints (checkpoint.py; DESIGN.md "Checkpoint and resume") ----------------------
+    agent_kind = ""
+
+    def _parts(self) -> dict:
+        """The stateful pieces by the prefix of their names in the learner's ``state_dict()``."""
+        parts = {"env": self.env, "replay": self.replay}
+        if self.fused is not None:
+            parts["update"] = self.fused
+        if self.stats is not None:
+            parts["stats"] = self.stats
+        if self.curriculum is not None:
+            parts["curriculum"] = self.curriculum
+        return parts
+
+    def state_dict(self) -> dict:
+        """The whole run, flat: ``<part>.<name>`` of every piece of ``_parts()``; without a fused
+        update the networks (``q.*`` / ``target.*``) and torch.optim.Adam's state per parameter name
+        (``adam.*``); the learner's generator (``gen``); and the learner's own counters
+        (``learner.*``, among them ``captured``: whether a captured learner wrote them)."""
+        out = {}
+        for prefix, part in self._parts().items():
+            for k, v in part.state_dict().items():
+                out[f"{prefix}.{k}"] = v
+        if self.fused is None:
+            for prefix, net in (("q", self.q), ("target", self.target)):
+                for k, v in net.state_dict().items():
+                    out[f"{prefix}.{k}"] = checkpoint.cpu_copy(v)
+            started = True
+            for name, p in self.q.named_parameters():
+                st = self.opt.state.get(p, {})
+                started = started and len(st) > 0
+                for k in ("exp_avg", "exp_avg_sq"):
+                    out[f"adam.{k}.{name}"] = checkpoint.cpu_copy(st[k] if st else torch.zeros_like(p))
+                step = st["step"] if st else torch.zeros(())
+                out[f"adam.step.{name}"] = torch.as_tensor(step).detach().to("cpu", torch.float32, copy=True).reshape(1)
+            out["adam.started"] = bool(started)
+        out["gen"] = checkpoint.cpu_copy(self.gen.get_state())
+        loss = self.last_loss
+        out["learner.last_loss"] = (torch.zeros(1) if loss is None
+                                    else loss.detach().to("cpu", torch.float32, copy=True).reshape(1))
+        out["learner.has_loss"] = loss is not None
+        out["learner.captured"] = self._graph is not None
+        for k, v in self._own_state().items():
+            out[f"learner.{k}"] = v
+        return out
+
+    def _check_loadable(self, host: dict) -> None:
+        """The learner's own refusals, from the file's host values, before anything is written.  A
+        captured frame holds the env's seed and offset as launch arguments, so a learner that is
+        already captured takes only a checkpoint with the same ones."""
+        if self._graph is not None:
+            env = self.env
+            for k in ("seed", "env_offset"):
+                if int(host[f"env.{k}"]) != int(getattr(env, k)):
+                    raise ValueError(f"checkpoint mismatch: env.{k} (file {host[f'env.{k}']}, learner {getattr(env, k)}): "
+                                     "the captured frame holds it as a launch argument; load into a fresh learner "
+                                     "and capture() after the load")
+            self._check_loadable_captured(host)
+
+    def _check_loadable_captured(self, host: dict) -> None:
+        pass
+
+    def load_state_dict(self, sd: dict) -> None:
+        """In place, piece by piece; then the device counters are refilled from the host's values
+        (``_load_counters``; ``capture()`` builds them from the same values)."""
+        for prefix, part in self._parts().items():
+            part.load_state_dict({k[len(prefix) + 1:]: v for k, v in sd.items() if k.startswith(prefix + ".")})
+        if self.fused is None:
+            with torch.no_grad():
+                for prefix, net in (("q", self.q), ("target", self.target)):
+                    for k, v in net.state_dict().items():
+                        v.copy_(sd[f"{prefix}.{k}"])
+                g = self.opt.param_groups[0]
+                on_device = bool(g.get("capturable") or g.get("fused"))
+                for name, p in self.q.named_parameters():
+                    st = self.opt.state[p]
+                    if not sd["adam.started"]:      # saved before the first update: Adam's state at step 0
+                        for t in st.values():
+                            t.zero_()
+                        continue
+                    if not st:      # as torch.optim.Adam creates it at its first step
+                        st["step"] = (torch.zeros((), dtype=torch.float32, device=p.device) if on_device
+                                      else torch.tensor(0.0, dtype=torch.float32))
+                        st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                        st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st["exp_avg"].copy_(sd[f"adam.exp_avg.{name}"])
+                    st["exp_avg_sq"].copy_(sd[f"adam.exp_avg_sq.{name}"])
+                    st["step"].copy_(sd[f"adam.step.{name}"].reshape(()))
+        self.gen.set_state(sd["gen"])
+        if not sd["learner.has_loss"]:
+            self.last_loss = None
+        elif self.fused is not None:
+            self.last_loss = self.fused.loss[0]
+        else:
+            self.last_loss = sd["learner.last_loss"].to(self.env.device)[0]
+        self._load_own_state({k[len("learner."):]: v for k, v in sd.items() if k.startswith("learner.")})
+        self._load_counters()
+
+    def _load_counters(self) -> None:
+        """The host mirrors are authoritative: the device counters that exist are refilled from them
+        (``_eps32`` as the ``.float()`` of the double, one rounding, as ``_capture_counters`` has it)."""
+        env, rp = self.env, self.replay
+        for name, v in (("_pos_t", rp.pos), ("_size_t", rp.size)):
+            if getattr(self, name, None) is not None:
+                getattr(self, name).fill_(v)
+        if self._graph is not None:
+            self._step_t.fill_(env.step_index)
+            self._eps64.fill_(self.epsilon)
+            self._eps32.copy_(self._eps64.float())
+            if self._tgt_prev is not None:       # (the settle law's carried targets: the env's, at a frame boundary)
+                self._tgt_prev.copy_(env.target)
+
+    def save(self, path: str) -> None:
+        """Write the run to ``path`` (checkpoint.py): one ``.npz``, moved into place when complete."""
+        checkpoint.save(self, path)
+
+    def load(self, path: str) -> dict:
+        """Put back a run saved by a learner built with the same arguments; a ValueError naming what
+        differs, before anything is written, otherwise.  Returns the file's header."""
+        return checkpoint.load(self, path)
 
     def _mirror_frame(self) -> None:
         """The host's copies of the counters after one replayed frame."""

@@ -40,6 +40,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from .agent import BatchedBDQ, BranchingQNetwork
+from .checkpoint import cpu_copy
 from .fused import FusedUpdate, bump
 from .learner import FrameLearner
 from .vector_env import VectorPBNEnv
@@ -62,6 +63,20 @@ class DeviceReplay:
         self.done = torch.zeros(capacity, dtype=torch.uint8, device=dev)
         self.pos = 0
         self.size = 0
+
+    _STATE_TENSORS = ("state", "next_state", "target", "action", "reward", "done")
+
+    def state_dict(self) -> dict:
+        """CPU copies of the ring's arrays, and ``pos`` and ``size``."""
+        out = {k: cpu_copy(getattr(self, k)) for k in self._STATE_TENSORS}
+        out.update(pos=int(self.pos), size=int(self.size))
+        return out
+
+    def load_state_dict(self, sd: dict) -> None:
+        """In place (a captured frame and ``_lib.RingStore`` hold the arrays' pointers)."""
+        for k in self._STATE_TENSORS:
+            getattr(self, k).copy_(sd[k])
+        self.pos, self.size = int(sd["pos"]), int(sd["size"])
 
     def _slots(self, n: int) -> torch.Tensor:
         return (torch.arange(n, device=self.device, dtype=torch.int64) + self.pos) % self.capacity
@@ -239,6 +254,19 @@ class PrioritisedDeviceReplay(DeviceReplay):
         self.beta_t = torch.full((1,), self.beta, dtype=torch.float64, device=dev)
         self.seed = int(seed)
         self.counter_t = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    _STATE_TENSORS = DeviceReplay._STATE_TENSORS + ("sum_tree", "min_tree", "max_priority", "counter_t")
+
+    def state_dict(self) -> dict:
+        """DeviceReplay's, the two trees whole (float64), ``max_priority``, the draw counter and the
+        host's ``beta``.  ``beta_t`` is not saved: the learner sets it from its host beta by its mode."""
+        out = super().state_dict()
+        out["beta"] = float(self.beta)
+        return out
+
+    def load_state_dict(self, sd: dict) -> None:
+        super().load_state_dict(sd)
+        self.beta = float(sd["beta"])
 
     def _i64(self, v: int) -> torch.Tensor:
         return torch.full((1,), v, dtype=torch.int64, device=self.device)
@@ -667,7 +695,12 @@ class BDQLearner(FrameLearner):
             # prioritised one: a prioritised sample depends on the priorities the update before
             # it wrote, so every update samples for itself)
             self._draw_t = torch.zeros(1, dtype=torch.int64, device=env.device)
-            self._idx = torch.empty(updates_per_frame * batch_size, dtype=torch.int64, device=env.device)
+            self._idx = torch.zeros(updates_per_frame * batch_size, dtype=torch.int64, device=env.device)
+        # the host's mirror of the draw counter at a frame boundary: the draws completed frames have
+        # consumed (a captured frame's last launch has already drawn the next frame's rows, so there
+        # *_draw_t is one ahead of it)
+        self.draws = 0
+        self._loaded_at: Optional[int] = None    # ``updates`` when a checkpoint was loaded
         self.last_loss: Optional[torch.Tensor] = None
         self.graphable = graphable
         self._graph: Optional[torch.cuda.CUDAGraph] = None
@@ -718,6 +751,7 @@ class BDQLearner(FrameLearner):
             if self.fused is not None and not self.prioritised:
                 size_t = torch.full((1,), self.replay.size, dtype=torch.int64, device=env.device)
                 self.replay.sample_rows(self._idx, self.seed, self._draw_t, size_t)
+                self.draws += 1
             for u in range(self.updates_per_frame):
                 if self.prioritised:
                     self.last_loss = self._update_prioritised()
@@ -783,7 +817,12 @@ class BDQLearner(FrameLearner):
             raise ValueError("target_update must be a multiple of updates_per_frame")
         env = self.env
         dev = env.device
-        self._warm_up(lambda: self.replay.size >= self.learning_starts and self.updates >= min_updates)
+        # a loaded checkpoint that already learns runs no eager frame here; with the PyTorch update it
+        # runs ``min_updates`` of them all the same: they initialise autograd's and the BLAS library's
+        # workspaces in this process, which a capture cannot
+        cold = self.fused is None and self._loaded_at is not None
+        self._warm_up(lambda: self.replay.size >= self.learning_starts and self.updates >= min_updates
+                      and not (cold and self.updates - self._loaded_at < min_updates))
         self._capture_counters(self.epsilon_final, self.epsilon_step, self.seed)
         self._done_buf = torch.zeros(env.n_alloc, dtype=torch.uint8, device=dev)
         self._capture_ring(_lib.FLAG_TERMINATED | _lib.FLAG_TRUNCATED, self._done_buf, self.agent.actions)
@@ -855,8 +894,97 @@ class BDQLearner(FrameLearner):
                 rp.mirror_beta()
         self.frames += 1
         self.updates += self.updates_per_frame
+        if self._adv is not None:
+            self.draws += 1
         if self.updates % self.target_update == 0:
             self._soft_update()
         reward, done, self.last_loss = self._g_out
         return reward, done
+
+    def run(self, k: int):
+        """``k`` captured frames replayed back to back (DDQNLearner.run's counterpart); returns the
+        last frame's (reward, done), as ``frame()`` does.  The soft target update stays on the host
+        (it falls due every ``target_update`` updates, 10,000 by default: a due test on the device
+        would add a launch to every frame), so the ``k`` frames are split where one falls due: each
+        segment is replayed with nothing on the host between its frames, then the host's copies
+        move on by the segment's frames with ``_replay_frame``'s own arithmetic, and the soft update
+        runs before the next segment."""
+        if self._graph is None:
+            raise ValueError("run() replays the captured frame: call capture() first")
+        if k < 1:
+            raise ValueError("k must be >= 1")
+        rp, U, T = self.replay, self.updates_per_frame, self.target_update
+        if self.fused is not None:
+            self.fused.sync()            # weights loaded between replays: repack the tables
+        else:
+            self._target_weights()       # (refreshes the captured head-weight copies if stale)
+        left = int(k)
+        while left:
+            # capture() made sure that T is a multiple of U, and updates moves by U a frame
+            n = min(left, max(1, (T - self.updates % T) // U))
+            for _ in range(n):
+                self._graph.replay()
+            if self.fused is not None:
+                self.fused.mark_updated()
+            else:
+                bump(self.q.parameters())
+            for _ in range(n):
+                self._mirror_frame()
+                if self.prioritised:
+                    for _ in range(U):
+                        rp.mirror_beta()
+            self.frames += n
+            self.updates += n * U
+            if self._adv is not None:
+                self.draws += n
+            if self.updates % T == 0:
+                self._soft_update()
+            left -= n
+        reward, done, self.last_loss = self._g_out
+        return reward, done
+
+    # ---- checkpoints (learner.py, checkpoint.py) ---------------------------------------------
+    agent_kind = "bdq"
+
+    def _predraws(self) -> bool:
+        """The fused uniform learner: its rows come from the REPLAY Philox stream, a frame ahead
+        when captured."""
+        return self.fused is not None and not self.prioritised
+
+    def _own_state(self) -> dict:
+        own = {"frames": int(self.frames), "updates": int(self.updates), "epsilon": self.epsilon}
+        if self._predraws():
+            own["draws"] = int(self.draws)
+            own["idx"] = cpu_copy(self._idx)
+        return own
+
+    def _check_loadable_captured(self, host: dict) -> None:
+        if int(host["replay.size"]) < self.learning_starts:
+            raise ValueError("the checkpoint was saved before learning started (fewer than learning_starts rows): "
+                             "a captured frame always updates; load into a learner that is not captured yet")
+        if int(host["learner.updates"]) % self.updates_per_frame:
+            raise ValueError("checkpoint mismatch: updates is not a multiple of updates_per_frame")
+
+    def _load_own_state(self, own: dict) -> None:
+        self.frames, self.updates, self.epsilon = int(own["frames"]), int(own["updates"]), own["epsilon"]
+        self._loaded_at = self.updates
+        rp, env = self.replay, self.env
+        if self.prioritised:
+            rp.beta_t.fill_(rp.beta)     # (moved by every sample, eager or captured: the host's copy is it)
+        if self.fused is None:
+            self._refresh_target_weights()
+        if not self._predraws():
+            return
+        self.draws = int(own["draws"])
+        self._draw_t.fill_(self.draws)
+        self._idx.copy_(own["idx"])
+        if self._graph is None:
+            return       # the eager frame draws at its start, capture() its first rows: both from draws
+        if own["captured"]:
+            self._draw_t.fill_(self.draws + 1)      # the saved rows are the next frame's: verbatim
+        else:
+            # an eager learner's rows are its last frame's: the next frame's are drawn now, over the
+            # fill level that frame's store will leave (as capture() draws its first)
+            first = torch.full((1,), min(rp.size + env.n_alloc, rp.capacity), dtype=torch.int64, device=env.device)
+            rp.sample_rows(self._idx, self.seed, self._draw_t, first)
 

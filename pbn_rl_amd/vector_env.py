@@ -335,5 +335,26 @@ class VectorPBNEnv:
         self.net.close()
         self.net, self.spec = net, spec
 
+    # ------------------------------------------------------------ checkpoints
+    _STATE_TENSORS = ("state", "target", "t", "flags", "reward", "final_state", "flipmask")
+
+    def state_dict(self) -> dict:
+        """CPU copies of the env's buffers (all ``n_alloc`` envs: the padding envs are stored in a
+        learner's ring like the others), ``step_index``, ``seed`` and ``env_offset``."""
+        out = {k: getattr(self, k).detach().to("cpu", copy=True) for k in self._STATE_TENSORS
+               if getattr(self, k) is not None}
+        out.update(step_index=int(self.step_index), seed=int(self.seed), env_offset=int(self.env_offset))
+        return out
+
+    def load_state_dict(self, sd: dict) -> None:
+        """In place: into whichever buffer is ``state`` now (the eager step swaps ``state`` and
+        ``_state_next``), so pointers held elsewhere stay valid."""
+        for k in self._STATE_TENSORS:
+            if getattr(self, k) is not None:
+                getattr(self, k).copy_(sd[k])
+        self.step_index = int(sd["step_index"])
+        self.seed = int(sd["seed"]) & 0xFFFFFFFFFFFFFFFF
+        self.env_offset = int(sd["env_offset"])
+
     def close(self) -> None:
         self.net.close()
