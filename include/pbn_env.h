@@ -943,6 +943,59 @@ int pbn_curriculum_redraw(const pbn_net* net, uint64_t seed, uint64_t step, cons
 int pbn_curriculum_refresh(const int64_t* d_totals, const int64_t* d_pairs, int32_t n_attr, int32_t horizon,
                            int64_t refresh_every, void* d_table, void* stream);
 
+/*
+ * The GBDQ graph agent's front (gbdq_model/network.py:73-79; DESIGN.md "GBDQ"): the three
+ * EdgeConv(add) + BatchNorm1d (training mode, one env at a time) + ReLU layers from the packed state,
+ * one launch, the activations in LDS (csrc/pbn_gbdq.hip; layouts and LDS carving: csrc/gbdq_front.h).
+ * Additive exports (the ABI version is unchanged).  N = the net's nodes.
+ *
+ * pbn_gbdq_pack builds the kernel's image (pbn_gbdq_image_floats floats, 16-byte aligned) from
+ *   d_conv      in  float, flat, in this order: for layer l = 1, 2, 3 the conv model's first Linear
+ *                   weight [64][in_l] and bias [64], its second Linear weight [N][64] and bias [N]
+ *                   (in_1 = 4, in_2 = in_3 = 2 N); then BatchNorm weight [N] and bias [N] of bn1, bn2, bn3
+ *   d_csr_start in  int32 [N + 1], d_csr_src int32 [n_edges]: the edge list grouped by target node:
+ *                   node i receives, in this order, the messages of the source nodes
+ *                   d_csr_src[d_csr_start[i] .. d_csr_start[i + 1])
+ * The image holds the layer-1 message table M1[16][N] (row = s_i | t_i << 1 | s_j << 2 | t_j << 3,
+ * computed in fp32 with sequential, unfused sums: over the 4 inputs from 0, then + bias, ReLU, over
+ * the 64 hidden units from 0, then + bias), layers 2 and 3 as [A - Bm | Bm] (the first Linear split
+ * in its x_i and x_j - x_i halves) and the transposed second Linear, zero-padded to the MFMA tiles.
+ *
+ * pbn_gbdq_front: d_out float [n][N N], row e = the (N, N) activations after bn3 + ReLU of env e's
+ * observation (node features (state bit, bit of the target attractor's first state; zeros for a
+ * target id without an attractor)), each BatchNorm normalising every (env, node) row over its own N
+ * features (biased variance, eps 1e-5).  Every sum has a fixed order: two runs give the same bits.
+ * n_envs a multiple of 32, n_envs N N < 2^31; d_image and d_out 16-byte aligned.  PBN_EINVAL when the
+ * LDS carving of gbdq_front.h does not fit one block.
+ */
+int pbn_gbdq_image_floats(const pbn_net* net, int32_t n_edges, int64_t* n_floats);
+int pbn_gbdq_pack(const pbn_net* net, const float* d_conv, int32_t n_edges, const int32_t* d_csr_start,
+                  const int32_t* d_csr_src, float* d_image, void* stream);
+int pbn_gbdq_front(const pbn_net* net, int64_t n_envs, const uint32_t* d_state, const uint8_t* d_target,
+                   const float* d_image, float* d_out, void* stream);
+
+/*
+ * pbn_replay_store into two rings (gbdq_model/__init__.py:183-200: terminated transitions go to
+ * memory_positive, all others to memory_negative), a stable partition in env order: with
+ * terminated_e = (d_flags[e] & term_mask) != 0, the r-th terminated env goes to slot
+ * (*d_pos_p + r) mod capacity_p of the positive ring, the r-th other env to slot
+ * (*d_pos_n + r) mod capacity_n of the negative ring; the stored done is (d_flags[e] & done_mask) != 0.
+ * Ring arrays as pbn_replay_store's.  Three launches on `stream`, no atomics and no waiting between
+ * blocks: per-block counts into d_work (int32 [ceil(n / 256)]); every block adds the counts of the
+ * blocks before it, in order, and stores its rows; one thread then writes d_counts (int64 [2]: the
+ * positive and the negative count) and advances both rings: *d_pos = (*d_pos + count) mod capacity,
+ * *d_size = min(*d_size + count, capacity).  Both capacities >= n; term_mask and done_mask nonzero.
+ */
+int pbn_replay_store_split(int64_t n, int32_t words, int32_t n_branches, const uint32_t* d_state,
+                           const uint32_t* d_next_state, const uint8_t* d_target, const int32_t* d_action,
+                           const float* d_reward, const uint8_t* d_flags, uint32_t term_mask, uint32_t done_mask,
+                           int64_t capacity_p, int64_t* d_pos_p, int64_t* d_size_p, uint32_t* d_ring_state_p,
+                           uint32_t* d_ring_next_state_p, uint8_t* d_ring_target_p, int32_t* d_ring_action_p,
+                           float* d_ring_reward_p, uint8_t* d_ring_done_p, int64_t capacity_n, int64_t* d_pos_n,
+                           int64_t* d_size_n, uint32_t* d_ring_state_n, uint32_t* d_ring_next_state_n,
+                           uint8_t* d_ring_target_n, int32_t* d_ring_action_n, float* d_ring_reward_n,
+                           uint8_t* d_ring_done_n, int32_t* d_work, int64_t* d_counts, void* stream);
+
 const char* pbn_last_error(void);
 int pbn_abi_version(void);
 
