@@ -18,6 +18,10 @@
 // v_mfma_f32_16x16x4_f32: exact f32 (an fmaf chain over k).  Lane l gives A[l & 15][k = l >> 4] and
 // B[k = l >> 4][l & 15] and holds D[4 (l >> 4) + r][l & 15] in register r.
 // No floating-point atomics anywhere: every sum's order is fixed by the thread that owns it.
+// Every ReLU is dqn_scalar.h's pbn::relu (x < 0 ? 0 : x), never fmaxf, which drops a NaN: a non-finite
+// parameter gives the literal PyTorch forward's NaN rows (DESIGN.md "Non-finite values").  Padding
+// needs no mask for it: a 0 * NaN can only land in rows >= N of u / v (never read: the edge list is
+// held to [0, N - 1]) and in output tiles' rows / columns >= N (never stored).
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -26,6 +30,7 @@
 #include <algorithm>
 
 #include "../../include/pbn_env.h"
+#include "dqn_scalar.h"
 #include "gbdq_front.h"
 #include "host_check.h"
 #include "net_view.h"
@@ -66,7 +71,7 @@ __global__ void __launch_bounds__(256) gbdq_pack_kernel(GbdqLayout L, GbdqConv C
       h = (h + mul_rn(w1[4 * c + 1], in1));
       h = (h + mul_rn(w1[4 * c + 2], in2));
       h = (h + mul_rn(w1[4 * c + 3], in3));
-      h = fmaxf((h + conv[C.b1[0] + c]), 0.f);
+      h = pbn::relu(h + conv[C.b1[0] + c]);
       acc = (acc + mul_rn(w2[c], h));
     }
     image[L.m1 + idx] = (acc + conv[C.b2[0] + o]);
@@ -118,8 +123,8 @@ __device__ __forceinline__ void bn_relu(float* __restrict__ act, int N, int NS, 
     const float d0 = h0 ? x0 - mean : 0.f, d1 = h1 ? x1 - mean : 0.f;
     const float var = wave_sum(d0 * d0 + d1 * d1) / fn;
     const float scale = gb[i] / sqrtf(var + 1e-5f), beta = gb[N + i];
-    if (h0) row[lane] = fmaxf(d0 * scale + beta, 0.f);
-    if (h1) row[lane + 64] = fmaxf(d1 * scale + beta, 0.f);
+    if (h0) row[lane] = pbn::relu(d0 * scale + beta);
+    if (h1) row[lane + 64] = pbn::relu(d1 * scale + beta);
   }
 }
 
@@ -191,7 +196,7 @@ __global__ void __launch_bounds__(kGbdqThreads) gbdq_front_kernel(GbdqLayout L, 
         const int i = idx >> 6, c = idx & 63;
         const float ui = u[i * kGbdqUS + c];
         float s = 0.f;
-        for (int e = cs[i]; e < cs[i + 1]; ++e) s += fmaxf(ui + v[cj[e] * kGbdqUS + c], 0.f);
+        for (int e = cs[i]; e < cs[i + 1]; ++e) s += pbn::relu(ui + v[cj[e] * kGbdqUS + c]);
         u[i * kGbdqUS + c] = s;
       }
       __syncthreads();

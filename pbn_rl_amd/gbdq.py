@@ -79,8 +79,10 @@ class EdgeConv(nn.Module):
     """``torch_geometric.nn.EdgeConv(nn, aggr="add")``, flow source -> target: for edge e with j =
     edge_index[0][e] and i = edge_index[1][e] the message is ``nn(cat[x_i, x_j - x_i])`` and node i's
     output the sum of the messages that end in it (zero without one).  x is (B, N, F) with one shared
-    edge list.  The gathers and the sum are products with 0/1 matrices: exact for the gathers, and with
-    a deterministic backward on the GPU (an index_add's atomics are not)."""
+    edge list.  The gathers and the sum are products with 0/1 matrices: exact for the gathers of finite
+    values, and with a deterministic backward on the GPU (an index_add's atomics are not).  A NaN or
+    infinite row of x reaches every node (0 * NaN), where an index gather, and pbn_gbdq_front, reach
+    only the nodes that receive from it (DESIGN.md "Non-finite values")."""
 
     def __init__(self, nn_module: nn.Module, aggr: str = "add"):
         super().__init__()

@@ -5,7 +5,6 @@ torch, one row per (env, edge)) to the float64 literal forward on the same input
 distance to float64 is at most 8 e_ref.  The margin covers the reordered sums, the pre-combined A - Bm
 and the division by a small per-row deviation; the measured ratios are in DESIGN.md "GBDQ"."""
 import copy
-import ctypes
 
 import numpy as np
 import pytest
@@ -19,65 +18,8 @@ from tests import gbdq_cases as gc
 
 pytestmark = pytest.mark.gpu
 
-CANARY = -12345.5
-DEV = "cuda"
-
-
-def _al16(v):
-    return (v + 15) & ~15
-
-
-def image_offsets(N):
-    """csrc/gbdq_front.h's image layout."""
-    Np, Kp = _al16(N), (N + 3) & ~3
-    o = {"m1": 0}
-    at = _al16(16 * N)
-    o["bn"] = at
-    at += _al16(6 * N)
-    for l in (0, 1):
-        o[f"wu{l}"] = at
-        at += _al16(Kp * 128)
-        o[f"b1{l}"] = at
-        at += 64
-        o[f"w2t{l}"] = at
-        at += _al16(64 * Np)
-        o[f"b2{l}"] = at
-        at += _al16(N)
-    o["csr_start"] = at
-    at += _al16(N + 1)
-    o["csr_src"] = at
-    return o, Np, Kp
-
-
-def pack_image(net, spec, q):
-    L = _lib.load()
-    N = spec.n
-    start, src = edge_csr(edge_index(spec), N)
-    nf = ctypes.c_int64()
-    _lib.check(L.pbn_gbdq_image_floats(net.handle, src.numel(), ctypes.byref(nf)), "pbn_gbdq_image_floats")
-    assert nf.value == image_offsets(N)[0]["csr_src"] + _al16(src.numel())
-    image = torch.full((nf.value + 64,), CANARY, dtype=torch.float32, device=DEV)
-    flat = q.conv_flat().to(DEV)
-    start_d, src_d = start.to(DEV), src.to(DEV)
-    _lib.check(L.pbn_gbdq_pack(net.handle, flat.data_ptr(), src.numel(), start_d.data_ptr(), src_d.data_ptr(),
-                               image.data_ptr(), torch.cuda.current_stream().cuda_stream), "pbn_gbdq_pack")
-    torch.cuda.synchronize()
-    assert torch.equal(image[nf.value:].cpu(), torch.full((64,), CANARY))
-    return image, nf.value
-
-
-def run_front(net, spec, image, words, target):
-    L = _lib.load()
-    n, N = words.shape[1], spec.n
-    st = torch.from_numpy(words.view(np.int32)).to(DEV)
-    tg = torch.from_numpy(target).to(DEV)
-    out = torch.full((n * N * N + 256,), CANARY, dtype=torch.float32, device=DEV)
-    _lib.check(L.pbn_gbdq_front(net.handle, n, st.data_ptr(), tg.data_ptr(), image.data_ptr(), out.data_ptr(),
-                                torch.cuda.current_stream().cuda_stream), "pbn_gbdq_front")
-    torch.cuda.synchronize()
-    got = out.cpu()
-    assert torch.equal(got[n * N * N:], torch.full((256,), CANARY))
-    return got[: n * N * N].reshape(n, N * N)
+CANARY, DEV = gc.CANARY, gc.DEV
+image_offsets, pack_image, run_front = gc.image_offsets, gc.pack_image, gc.run_front      # (shared with the edge sweep)
 
 
 @pytest.fixture(scope="module")
@@ -116,10 +58,11 @@ def test_front_kernel_within_eight_times_the_fp32_error(nets, name, n, bn):
     assert torch.equal(got.view(torch.int32), again.view(torch.int32))       # two runs, equal bits
 
 
-@pytest.mark.parametrize("name", ["pbn7", "pbn70", "hub"])
+@pytest.mark.parametrize("name", ["pbn7", "pbn70", "hub", "size64", "size65", "size128"])
 def test_front_kernel_zero_variance_gives_relu_beta(nets, name):
     """Zero conv weights with constant biases: every (env, node) row is constant, its variance zero,
-    and the output relu(beta) exactly, without a NaN."""
+    and the output relu(beta) exactly, without a NaN.  (size64 / size65: the last N with one feature
+    per lane and the first with two; size128: both features on every lane.)"""
     spec, net = nets(name)
     N = spec.n
     q = gc.make_q(N, 5, 3, bn="random")
@@ -138,31 +81,18 @@ def test_front_kernel_zero_variance_gives_relu_beta(nets, name):
     assert torch.isfinite(got).all() and torch.equal(got, want)
 
 
-@pytest.mark.parametrize("name", ["pbn7", "pbn70"])
+@pytest.mark.parametrize("name", ["pbn7", "pbn70", "size16", "size65", "size128"])
 def test_pack_table_and_segments_bit_for_bit(nets, name):
     """M1 against the sequential, unfused fp32 sums the header states; the [A - Bm | Bm] and transposed
-    second-Linear segments with their zero padding; the edge list."""
+    second-Linear segments with their zero padding; the edge list.  (size16, size128: full tiles, no
+    zero padding at all; size65: a Kp-row tail of three zero rows and 15 zero tile columns.)"""
     spec, net = nets(name)
     N = spec.n
     q = gc.make_q(N, 5, 17, bn="random")
     image, nf = pack_image(net, spec, q)
     img = image[:nf].cpu().numpy()
     off, Np, Kp = image_offsets(N)
-    f32 = np.float32
-    w1, b1 = q.conv_model1[0].weight.detach().numpy(), q.conv_model1[0].bias.detach().numpy()
-    w2, b2 = q.conv_model1[2].weight.detach().numpy(), q.conv_model1[2].bias.detach().numpy()
-    want = np.zeros((16, N), dtype=f32)
-    for code in range(16):
-        si, ti, sj, tj = (f32((code >> b) & 1) for b in range(4))
-        inp = [si, ti, f32(sj - si), f32(tj - ti)]
-        acc = np.zeros(N, dtype=f32)
-        for c in range(64):
-            h = f32(w1[c, 0] * inp[0])
-            for k in (1, 2, 3):
-                h = f32(h + f32(w1[c, k] * inp[k]))
-            h = max(f32(h + b1[c]), f32(0))
-            acc = (acc + (w2[:, c] * h).astype(f32)).astype(f32)
-        want[code] = (acc + b2).astype(f32)
+    want = gc.m1_table_numpy(q)     # (F.relu's law, x < 0 ? 0 : x: equal to max(x, 0) on these finite sums)
     assert np.array_equal(img[: 16 * N].reshape(16, N), want)
     for l, m in ((0, q.conv_model2), (1, q.conv_model3)):
         W1, W2 = m[0].weight.detach().numpy(), m[2].weight.detach().numpy()
