@@ -1,5 +1,5 @@
 """Inputs and float64 references of the replay-path edge sweeps (test_gpu_replay_edges.py,
-test_gpu_per_edges.py), built on the CPU so that test_replay_edges_host.py can check, from the oracle
+test_gpu_per_edges.py, the store of test_gpu_grid_caps.py), built on the CPU so that test_replay_edges_host.py can check, from the oracle
 and the references alone, the conditions under which a wrong kernel cannot pass:
 
   TD loss      synthetic head tensors at every (B, K, A) where td_loss_kernel changes path: a partial
@@ -10,6 +10,8 @@ and the references alone, the conditions under which a wrong kernel cannot pass:
   PER samples  (capacity, size, seed, batches): priorities spread over six decades, the seed picked
                so that p_total's association matters and every large batch reaches both halves;
                and one constructed tree on which the association decides a sampled row.
+  ring store   random transitions and the ring pbn_replay_store leaves of them, in numpy (the store past
+               its grid cap: test_gpu_grid_caps.py).
   gather       rings over edge_spec(N) whose rows set and clear bit N - 1, with target ids on both
                sides of n_attr.
 """
@@ -241,9 +243,48 @@ def association_oracle():
     return ctr, o
 
 
+# ---- ring store ------------------------------------------------------------------------------
+
+STORE_FIELDS = ("state", "next_state", "target", "action", "reward", "done")
+STORE_CANARY = {"state": 0xF9F9F9F9, "next_state": 0xF9F9F9F9, "target": 0xEE, "action": -7, "reward": -7.0,
+                "done": 0xEE}
+
+
+def store_transitions(n, W, K, seed):
+    """n random transitions as numpy arrays: state / next_state (W, n) uint32, target (n,) uint8,
+    action (n, K) int32, reward (n,) float32, done (n,) uint8 flag bytes (any of the low six bits)."""
+    rng = np.random.default_rng(seed)
+    word = lambda: rng.integers(0, 2 ** 32, size=(W, n), dtype=np.uint64).astype(np.uint32)  # noqa: E731
+    return {"state": word(), "next_state": word(), "target": rng.integers(0, 256, size=n).astype(np.uint8),
+            "action": rng.integers(0, 129, size=(n, K)).astype(np.int32),
+            "reward": rng.standard_normal(n).astype(np.float32), "done": rng.integers(0, 64, size=n).astype(np.uint8)}
+
+
+def store_expected(cap, W, K, pos, t, done_mask=0):
+    """(ring fields after pbn_replay_store of transitions t at slots (pos + e) mod cap into a ring
+    of STORE_CANARY values, the 0 / 1 done values by row): done is flags & done_mask != 0, or
+    flags != 0 when done_mask is 0."""
+    n = t["target"].shape[0]
+    slots = (pos + np.arange(n, dtype=np.int64)) % cap
+    done01 = ((t["done"] & np.uint8(done_mask)) != 0 if done_mask else t["done"] != 0).astype(np.uint8)
+    ring = {"state": np.full((W, cap), STORE_CANARY["state"], np.uint32),
+            "next_state": np.full((W, cap), STORE_CANARY["next_state"], np.uint32),
+            "target": np.full(cap, STORE_CANARY["target"], np.uint8),
+            "action": np.full((cap, K), STORE_CANARY["action"], np.int32),
+            "reward": np.full(cap, STORE_CANARY["reward"], np.float32),
+            "done": np.full(cap, STORE_CANARY["done"], np.uint8)}
+    ring["state"][:, slots] = t["state"]
+    ring["next_state"][:, slots] = t["next_state"]
+    ring["target"][slots] = t["target"]
+    ring["action"][slots] = t["action"]
+    ring["reward"][slots] = t["reward"]
+    ring["done"][slots] = done01
+    return ring, done01
+
+
 # ---- batch gather ----------------------------------------------------------------------------
 
-GATHER_N = [31, 32, 33, 64, 65, 96, 97, 127]
+GATHER_N =[31, 32, 33, 64, 65, 96, 97, 127]
 GATHER_CAP = 61
 GATHER_B = [1, 33, 96]
 

@@ -183,8 +183,11 @@ def test_world1_ride_consumed_on_another_stream():
 
 
 def test_copy_async_entry_point():
-    """pbn_copy_async: ragged sizes (every 16-byte multiple up to a few vectors past the grid's
-    stride loop), offsets into a buffer, and its argument checks."""
+    """pbn_copy_async: ragged sizes (one vector; four blocks and three vectors; 4 MiB less seven
+    vectors, where the grid is not capped and every thread takes one unrolled trip but the last
+    seven, which take three single-vector ones), offsets into a buffer, and its argument checks.  No
+    thread here takes a second trip, or a single-vector tail after an unrolled trip:
+    test_gpu_grid_caps.py runs the sizes past the capped grid."""
     import ctypes
     from pbn_rl_amd import _lib
     L = _lib.load()
