@@ -27,6 +27,8 @@
  *        bdq_model/__init__.py:100-139                         -> pbn_bdq_learn (+ pbn_bdq_layout,
  *                                                                 pbn_bdq_pack, pbn_replay_store,
  *                                                                 pbn_replay_advance)
+ *   ControlGBDQ.predict (one binary value per control node)
+ *        control_gbdq_model/__init__.py:64-86                  -> pbn_gbdq_front, pbn_cgbdq_flipmask
  *   a frame loop captured once and replayed (no reference counterpart)
  *                                                              -> pbn_step_dev, pbn_q_to_flipmask_dev
  *   the hand-off of a rollout's transitions to the learner (north_star's per-rollout gather;
@@ -995,6 +997,47 @@ int pbn_replay_store_split(int64_t n, int32_t words, int32_t n_branches, const u
                            int64_t* d_size_n, uint32_t* d_ring_state_n, uint32_t* d_ring_next_state_n,
                            uint8_t* d_ring_target_n, int32_t* d_ring_action_n, float* d_ring_reward_n,
                            uint8_t* d_ring_done_n, int32_t* d_work, int64_t* d_counts, void* stream);
+
+/*
+ * The ControlGBDQ agent's tail (control_gbdq_model/network.py:43-78, control_gbdq_model/__init__.py:
+ * 64-86; DESIGN.md "ControlGBDQ"): Linear(N N, 256) + ReLU, two Linear(256, 256) + ReLU, a
+ * Linear(256, 1) value head and C = n_ctrl Linear(256, 2) advantage heads, in one MFMA launch
+ * (csrc/pbn_cgbdq.hip; parameter order, image layout and LDS carving: csrc/cgbdq_tail.h).  Additive
+ * exports (the ABI version is unchanged).  N = the net's nodes (at most 128), n_ctrl 1..128.
+ *
+ * pbn_cgbdq_pack builds the image (pbn_cgbdq_image_floats floats, 16-byte aligned) from
+ *   d_tail   in  float, flat, torch's (out, in) layout, in this order: model.0 weight [256][N N] and
+ *                bias [256], model.2 and model.4 weight [256][256] and bias [256], value_head weight
+ *                [256] and bias [1], then for head k = 0 .. C - 1 its weight [2][256] and bias [2]
+ * Every dense layer is stored as v_mfma_f32_16x16x4_f32 A fragments (a tile's four operands of 16
+ * inputs are one contiguous 1 KiB), the inputs beyond N N and the head rows beyond 1 + 2 C zero; the
+ * head rows are stacked, the value head first, then (head k, output a) at row 1 + 2 k + a.
+ *
+ * pbn_cgbdq_heads (for tests, as pbn_qnet_heads):
+ *   d_front  in   float [n][N N]: pbn_gbdq_front's output
+ *   d_heads  out  float [n][1 + 2 C]: the raw value and advantage outputs, rows as stacked above
+ *
+ * pbn_cgbdq_flipmask: the same layers by the same code (heads bit-equal to pbn_cgbdq_heads'), then per
+ * env and head k: mean = (adv_0 + adv_1) / 2, q_a = (v + adv_a) - mean, action = torch.argmax's (1 iff
+ * q_1 > q_0 or q_1 is NaN and q_0 is not); epsilon-greedy by the EXPLORE law (explore iff word 0 <
+ * floor(epsilon 2^32)): explore_mode 0 gives every head the value 0, 1 gives head k the value
+ * (word_{k + 1} 2) >> 32, words numbered across the stream's calls; then the control flip mask
+ *   d_ctrl_nodes in   int32 [C]: head k's node; an entry outside [0, N) keeps its head and sets no bit
+ *   d_state      in   uint32 [W][n]: the envs' packed states
+ *   d_flipmask   out  uint32 [W][n]: (state XOR values) AND control bits, values = OR of a_k << c_k
+ *   d_actions    out  int32 [n][C] (nullable): the chosen values
+ * d_step / d_epsilon: optional device pointers read when the kernel runs, as pbn_heads_to_flipmask's.
+ * No head output goes to HBM.  Every sum has a fixed order: two runs give the same bits.
+ * n_envs and env_offset multiples of 32, n_envs N N < 2^31; d_image 16-byte aligned.
+ */
+int pbn_cgbdq_image_floats(const pbn_net* net, int32_t n_ctrl, int64_t* n_floats);
+int pbn_cgbdq_pack(const pbn_net* net, const float* d_tail, int32_t n_ctrl, float* d_image, void* stream);
+int pbn_cgbdq_heads(const pbn_net* net, int64_t n_envs, const float* d_front, const float* d_image, int32_t n_ctrl,
+                    float* d_heads, void* stream);
+int pbn_cgbdq_flipmask(const pbn_net* net, uint64_t seed, uint64_t step, const uint64_t* d_step, uint64_t env_offset,
+                       int64_t n_envs, const float* d_front, const float* d_image, int32_t n_ctrl,
+                       const int32_t* d_ctrl_nodes, int32_t explore_mode, float epsilon, const float* d_epsilon,
+                       const uint32_t* d_state, uint32_t* d_flipmask, int32_t* d_actions, void* stream);
 
 const char* pbn_last_error(void);
 int pbn_abi_version(void);

@@ -28,7 +28,8 @@ FLAG_RESET = 16
 FLAG_UNSETTLED = 32
 
 SOURCES = ["pbn_env.hip", "pbn_settle.hip", "pbn_agent.hip", "pbn_qnet.hip", "pbn_learn.hip", "pbn_eval.hip",
-           "pbn_per.hip", "pbn_ddqn.hip", "pbn_table.hip", "pbn_episode.hip", "pbn_curriculum.hip", "pbn_gbdq.hip"]
+           "pbn_per.hip", "pbn_ddqn.hip", "pbn_table.hip", "pbn_episode.hip", "pbn_curriculum.hip", "pbn_gbdq.hip",
+           "pbn_cgbdq.hip"]
 
 _lib: Optional[ctypes.CDLL] = None
 

@@ -38,7 +38,7 @@ from .replay import DeviceReplay
 from .vector_env import actions_to_flipmask, unpack_states
 
 __all__ = ["edge_index", "edge_csr", "EdgeConv", "GraphBranchingQNetwork", "gbdq_update", "front_supported",
-           "SplitDeviceReplay", "BatchedGBDQ", "GBDQLearner"]
+           "ring_rows", "SplitDeviceReplay", "BatchedGBDQ", "GBDQLearner"]
 
 
 # ------------------------------------------------------------------------------------ the graph
@@ -225,6 +225,27 @@ def front_supported(n_nodes: int) -> bool:
 
 
 # ------------------------------------------------------------------------------------ the two rings
+def ring_rows(ring: DeviceReplay, idx: torch.Tensor, net_handle=None, spec=None) -> tuple:
+    """Rows ``idx`` of one ring as gbdq_update's columns (states, targets, next_states, actions, rewards,
+    masks).  On the GPU through pbn_replay_batch (the index list padded to a multiple of 32, the result
+    sliced); on the CPU the same rows unpacked in torch."""
+    B = idx.shape[0]
+    if ring.device.type == "cuda":
+        pad = (-B) % 32
+        full = torch.cat([idx, idx[:1].expand(pad)]) if pad else idx
+        g = ring.gather(full, net_handle)
+        Bp, x = full.shape[0], g["x"]
+        return (x[0, :B], x[1, :B], x[0, Bp:Bp + B], g["actions"][:B], g["rewards"][:B], g["masks"][:B])
+    spec = spec if spec is not None else net_handle.spec
+    N = spec.n
+    first = torch.zeros(len(spec.attractors) + 1, N)
+    for a, att in enumerate(spec.attractors):
+        first[a] = torch.tensor(list(att[0]), dtype=torch.float32)
+    tg = ring.target[idx].long().clamp(max=len(spec.attractors))
+    return (unpack_states(ring.state[:, idx], N).float(), first[tg], unpack_states(ring.next_state[:, idx], N).float(),
+            ring.action[idx].long().unsqueeze(-1), ring.reward[idx].reshape(-1, 1), ring.done[idx].float().reshape(-1, 1))
+
+
 class SplitDeviceReplay:
     """``memory_positive`` and ``memory_negative`` (gbdq_model/__init__.py:159-200): terminated
     transitions go to ``positive``, all others to ``negative`` (two DeviceReplay rings of ``capacity``
@@ -308,28 +329,8 @@ class SplitDeviceReplay:
     def gather(self, idx_p: torch.Tensor, idx_n: torch.Tensor, net_handle=None, spec=None) -> Dict[str, torch.Tensor]:
         """The rows as gbdq_update's batch, positive rows first (:101).  On the GPU through
         pbn_replay_batch (index lists padded to a multiple of 32, the result sliced)."""
-        parts = []
-        for ring, idx in ((self.positive, idx_p), (self.negative, idx_n)):
-            B = idx.shape[0]
-            if B == 0:
-                continue
-            if self.device.type == "cuda":
-                pad = (-B) % 32
-                full = torch.cat([idx, idx[:1].expand(pad)]) if pad else idx
-                g = ring.gather(full, net_handle)
-                Bp, x = full.shape[0], g["x"]
-                parts.append((x[0, :B], x[1, :B], x[0, Bp:Bp + B], g["actions"][:B], g["rewards"][:B], g["masks"][:B]))
-            else:
-                spec = spec if spec is not None else net_handle.spec
-                N = spec.n
-                first = torch.zeros(len(spec.attractors) + 1, N)
-                for a, att in enumerate(spec.attractors):
-                    first[a] = torch.tensor(list(att[0]), dtype=torch.float32)
-                tg = ring.target[idx].long().clamp(max=len(spec.attractors))
-                parts.append((unpack_states(ring.state[:, idx], N).float(), first[tg],
-                              unpack_states(ring.next_state[:, idx], N).float(),
-                              ring.action[idx].long().unsqueeze(-1), ring.reward[idx].reshape(-1, 1),
-                              ring.done[idx].float().reshape(-1, 1)))
+        parts = [ring_rows(ring, idx, net_handle, spec) for ring, idx in ((self.positive, idx_p), (self.negative, idx_n))
+                 if idx.shape[0]]
         cols = [torch.cat(c, 0) for c in zip(*parts)]
         return dict(zip(("states", "targets", "next_states", "actions", "rewards", "masks"), cols))
 
@@ -384,13 +385,20 @@ class BatchedGBDQ:
     the restated ``per_env=True`` forward stands in for the kernel."""
 
     def __init__(self, env, qnet: Optional[GraphBranchingQNetwork] = None, branches: int = 5, *, epsilon: float = 0.0):
+        N = env.n_nodes
+        q = (qnet if qnet is not None else GraphBranchingQNetwork(N, N + 1, int(branches))).to(torch.device(env.device))
+        if q.state != N or q.ac_dim != N + 1 or q.n != int(branches):
+            raise ValueError("BatchedGBDQ needs GraphBranchingQNetwork(N, N + 1, branches)")
+        self._init_front(env, q, branches, epsilon)
+
+    def _init_front(self, env, q, branches: int, epsilon: float) -> None:
+        """What every agent on this front shares: the edge list, the action buffer, the targets' first
+        states and, where the kernel runs, its image and output."""
         self.env = env
         N = env.n_nodes
         self.branches = int(branches)
         self.device = torch.device(env.device)
-        self.q = (qnet if qnet is not None else GraphBranchingQNetwork(N, N + 1, self.branches)).to(self.device)
-        if self.q.state != N or self.q.ac_dim != N + 1 or self.q.n != self.branches:
-            raise ValueError("BatchedGBDQ needs GraphBranchingQNetwork(N, N + 1, branches)")
+        self.q = q
         self.epsilon = float(epsilon)
         self.edges = edge_index(env.spec, device=self.device)
         n = env.n_alloc
@@ -415,6 +423,9 @@ class BatchedGBDQ:
                                   "update is PyTorch's (DESIGN.md 'GBDQ')")
 
     def pack(self) -> torch.Tensor:
+        return self._pack_front()
+
+    def _pack_front(self) -> torch.Tensor:
         """The front kernel's image, repacked (pbn_gbdq_pack) when a graph-layer parameter changed."""
         q = self.q
         ps = [p for m in (q.conv_model1, q.conv_model2, q.conv_model3, q.bn1, q.bn2, q.bn3) for p in m.parameters()]
@@ -442,7 +453,7 @@ class BatchedGBDQ:
         env = self.env
         if not self.kernel:
             return self.q.front(self.observe(), self.edges, per_env=True)
-        image = self.pack()
+        image = self._pack_front()
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().pbn_gbdq_front(env.net.handle, env.n_alloc, env.state.data_ptr(), env.target.data_ptr(),
                                                   image.data_ptr(), self._front.data_ptr(), env._stream()),
